@@ -6,16 +6,26 @@ Workload (the configuration the metric "at 64 policies"
 (string classification kernel + policy evaluation kernel) over the GPU's whole resident batch,
 producing 64M verdict words. Inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-      --master-port P bench.py --gpus N --steps K --warmup W
+      --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warmup steps, exactly K timed
+steps, the outputs if --dump-outputs is given, the JSON line (`value`, `ms_per_step`). --full adds
+every other measurement to that line: per-kernel device times and the roofline, the final verdicts'
+allowed fraction, the CPU baseline, the host timing modes (--no-cpu-baseline / --no-host-modes drop
+those two again) and, with several GPUs, the weak-scaling job and the verdict gather.
+--dump-outputs DIR writes the verdict words of the last timed step (a fixed, seeded sample of rows
+when they exceed 32 MiB) as DIR/verdicts.npy with the sampled row numbers in DIR/rows.npy, float64
+(exact for the 32-bit words); rank k > 0 of a multi-GPU run writes verdicts_rank<k>.npy / rows_rank<k>.npy.
+The inputs depend on the arguments and SEED alone, so two builds can be compared output for output.
 
 Multi-GPU: one process per GPU; rank 0 compiles the policy set and broadcasts the compiled-table
 blob once over RCCL (torch.distributed "nccl" = RCCL on ROCm); every rank evaluates its own request
 shard; no collective on the per-request path. With several GPUs and no size flag, `value` is BASELINE's
 own multi-GPU workload, strong scaling: the config's request count as ONE job sharded across the GPUs
-(C4: 1M requests over N GPUs; --config c5_mixed: 10M), and the same run then measures weak scaling
-(that many requests per GPU) as the `weak_scaling` field. --rows R (per GPU, weak) or --total-rows T
+(C4: 1M requests over N GPUs; --config c5_mixed: 10M), and with --full the same run also measures weak
+scaling (that many requests per GPU) as the `weak_scaling` field. --rows R (per GPU, weak) or --total-rows T
 (one job, strong) choose one measurement explicitly. Timing: barrier + synchronize on both sides of
 exactly K steps, max over ranks. Rank 0 prints one JSON line.
 """
@@ -31,6 +41,7 @@ sys.path.insert(0, os.path.join(ROOT, "policy-server_amd"))
 
 METRIC = "admission requests evaluated/sec (node) at 64 policies; HBM GB/s vs peak"
 SEED = 20250509
+DUMP_WORDS = 1 << 22  # --dump-outputs: at most this many verdict words per run (32 MiB as float64)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
 
 # BASELINE.json configs: policies file, synthetic workload id, default requests per GPU,
@@ -66,8 +77,13 @@ def main():
                     help="a fixed job of this many requests sharded across the GPUs (strong scaling)")
     ap.add_argument("--config", default="c4_64", choices=sorted(CONFIGS))
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (rank 0), about 10-30 s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-host-modes", action="store_true", help="skip the end-to-end / flatten timings")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-kernel times and roofline, "
+                         "allowed fraction, CPU baseline, host timing modes, multi-GPU weak scaling and gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's verdict words (a seeded row sample if large) to DIR/*.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: gloo, the host walk (kw_debug_host_walk) as the step over a 1/1000 sample of "
                          "the config's rows; exercises the argument path and the JSON fields only (tests)")
@@ -81,7 +97,7 @@ def main():
     if args.rows is None and args.total_rows is None:
         if world_env > 1:  # BASELINE's multi-GPU configs are fixed jobs: strong first, weak beside it
             args.total_rows = default_rows
-            also_weak = True
+            also_weak = args.full
         else:
             args.rows = default_rows
 
@@ -131,6 +147,7 @@ def main():
         batch = syn.batch() if dry else syn.batch().to_device(device)
         step = (lambda: batch.debug_host_walk(env, ids)) if dry else (lambda: batch.validate(env, ids))
         log(f"rank {rank}: {nrows} requests generated + resident in {time.time() - t0:.1f}s; {npol} policies ({scaling})")
+        out = None
         for _ in range(args.warmup):
             step()
         sync()
@@ -139,7 +156,7 @@ def main():
         sync()
         t_start = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            out = step()
         sync()
         if dist:
             dist.barrier()
@@ -148,65 +165,81 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if dry else "cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        return syn, batch, bounds, job_rows, scaling, nrows, elapsed
+        return syn, batch, bounds, job_rows, scaling, nrows, elapsed, out
 
     weak = None
     if also_weak:  # the weak-scaling field first (its batch is released before the primary job's)
-        wsyn, wbatch, _, wjob, _, wrows, welapsed = measure(rows_per_rank=default_rows)
+        wsyn, wbatch, _, wjob, _, wrows, welapsed, _ = measure(rows_per_rank=default_rows)
         weak = {"value": wjob * args.steps / welapsed, "unit": "requests/s", "ms_per_step": welapsed * 1e3 / args.steps,
                 "requests_per_gpu": wrows, "total_requests": wjob, "scaling": "weak",
                 "workload": workload.format(rows=default_rows, npol=npol)}
         wbatch.close()
         del wsyn, wbatch
-    syn, batch, bounds, job_rows, scaling, nrows, elapsed = measure(total_rows=args.total_rows, rows_per_rank=args.rows)
+    syn, batch, bounds, job_rows, scaling, nrows, elapsed, last = measure(total_rows=args.total_rows,
+                                                                          rows_per_rank=args.rows)
     ms_per_step = elapsed * 1e3 / args.steps
     value = job_rows * args.steps / elapsed
+    if args.dump_outputs:
+        # the last timed step's verdict words, before any later pass over the batch (dry run: the host walk's)
+        dump_outputs(args.dump_outputs, last if dry else batch.verdicts(), nrows, npol, rank, world)
+    del last
 
-    # per-kernel device time with HIP events on the launch stream
+    # everything below the headline figure is measured with --full only
+    kernel_ms = roofline = gather = frac_allowed = cpu = modes = None
     if dry:
-        from types import SimpleNamespace
-        tm = SimpleNamespace(classify_ms=0.0, evaluate_ms=ms_per_step, total_ms=ms_per_step, classify_bytes=0.0,
-                             evaluate_bytes=0.0)
         args.no_cpu_baseline = args.no_host_modes = True
-    else:
-        tm = batch.timed(env, ids, warmup=2, reps=max(5, args.steps))
-    kernels = {"classify": (tm.classify_ms, tm.classify_bytes), "evaluate": (tm.evaluate_ms, tm.evaluate_bytes)}
-    dom = max(kernels, key=lambda k: kernels[k][0])
-    ms, nbytes = kernels[dom]
-    achieved = nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    gather = None
-    if dry:
-        frac_allowed = None
-    elif dist:
-        # verdict words back to the host after the timed region: each rank copies its shard D2H into
-        # its own disjoint slice of one shared host array (kwgpu.dist.gather_verdicts), rank 0 holds it
-        from kwgpu.dist import gather_verdicts
-        t = time.perf_counter()
-        allv = gather_verdicts(batch, bounds, npol, dist, rank, world, tensor_device="cuda")
+    if args.full:
+        # per-kernel device time with HIP events on the launch stream
+        if dry:
+            from types import SimpleNamespace
+            tm = SimpleNamespace(classify_ms=0.0, evaluate_ms=ms_per_step, total_ms=ms_per_step, classify_bytes=0.0,
+                                 evaluate_bytes=0.0)
+        else:
+            tm = batch.timed(env, ids, warmup=2, reps=max(5, args.steps))
+        kernels = {"classify": (tm.classify_ms, tm.classify_bytes), "evaluate": (tm.evaluate_ms, tm.evaluate_bytes)}
+        dom = max(kernels, key=lambda k: kernels[k][0])
+        ms, nbytes = kernels[dom]
+        achieved = nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+        if dry:
+            frac_allowed = None
+        elif dist:
+            # verdict words back to the host after the timed region: each rank copies its shard D2H into
+            # its own disjoint slice of one shared host array (kwgpu.dist.gather_verdicts), rank 0 holds it
+            from kwgpu.dist import gather_verdicts
+            t = time.perf_counter()
+            allv = gather_verdicts(batch, bounds, npol, dist, rank, world, tensor_device="cuda")
+            if rank == 0:
+                dt = time.perf_counter() - t
+                flat = allv.reshape(-1)
+                frac_allowed = sum(int(np.count_nonzero(flat[c:c + (1 << 26)] & K._native.KW_F_ALLOWED))
+                                   for c in range(0, flat.size, 1 << 26)) / max(flat.size, 1)
+                gather = {"rows": int(allv.shape[0]), "bytes": int(allv.nbytes), "s": dt,
+                          "GB_per_s": allv.nbytes / dt / 1e9,
+                          "how": "per-rank D2H into disjoint slices of one shared host file mapping"}
+                del allv
+        else:
+            v = batch.verdicts()
+            frac_allowed = float(((v & K._native.KW_F_ALLOWED) != 0).mean())
+            del v
         if rank == 0:
-            dt = time.perf_counter() - t
-            flat = allv.reshape(-1)
-            frac_allowed = sum(int(np.count_nonzero(flat[c:c + (1 << 26)] & K._native.KW_F_ALLOWED))
-                               for c in range(0, flat.size, 1 << 26)) / max(flat.size, 1)
-            gather = {"rows": int(allv.shape[0]), "bytes": int(allv.nbytes), "s": dt, "GB_per_s": allv.nbytes / dt / 1e9,
-                      "how": "per-rank D2H into disjoint slices of one shared host file mapping"}
-            del allv
-    else:
-        v = batch.verdicts()
-        frac_allowed = float(((v & K._native.KW_F_ALLOWED) != 0).mean())
-        del v
+            traffic_bytes, traffic_src = (None, "dry run") if dry else traffic(args, nrows)
+            if not args.no_cpu_baseline:
+                cpu = cpu_baseline(policies, ids, args)
+            modes = None if args.no_host_modes else host_modes(env, ids, syn, device, args, nbytes)
+            kernel_ms = {"classify": tm.classify_ms, "evaluate": tm.evaluate_ms, "total": tm.total_ms}
+            roofline = {"kernel": "evaluate_tiles_kernel",
+                        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_bytes,
+                        "traffic_source": traffic_src,
+                        "algorithmic_bytes_per_launch": nbytes, "algorithmic_bytes_per_request": nbytes / nrows}
 
     result = None
     if rank == 0:
-        traffic_bytes, traffic_src = (None, "dry run") if dry else traffic(args, nrows)
-        cpu = None
-        if not args.no_cpu_baseline:
-            cpu = cpu_baseline(policies, ids, args)
-        modes = None if args.no_host_modes else host_modes(env, ids, syn, device, args, nbytes)
         result = {
             "metric": METRIC, "value": value, "unit": "requests/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling,
             "vs_baseline": None, "dtype": "u8", "data": "synthetic" + (" (dry run: host walk, no GPU)" if dry else ""),
+            "full": args.full,
             "config": {"workload": (workload.format(rows=args.rows, npol=npol) if scaling == "weak" else
                                     workload.format(rows=job_rows, npol=npol).replace(" per GPU", "")
                                     + f", one job sharded across {world} GPU(s)"
@@ -214,12 +247,8 @@ def main():
                        "config": args.config, "requests_per_gpu": job_rows / world, "total_requests": job_rows,
                        "policies": npol, "parallelism": f"dp{world} (request shards)"},
             "evaluations_per_s": value * npol,
-            "kernel_ms": {"classify": tm.classify_ms, "evaluate": tm.evaluate_ms, "total": tm.total_ms},
-            "roofline": {"kernel": "evaluate_tiles_kernel",
-                         "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_bytes,
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": nbytes, "algorithmic_bytes_per_request": nbytes / nrows},
+            "kernel_ms": kernel_ms,
+            "roofline": roofline,
             "weak_scaling": weak,
             "cpu_baseline": cpu,
             "timing_modes": modes,
@@ -232,6 +261,25 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return result
+
+
+def dump_outputs(outdir, verdicts, nrows, npol, rank, world):
+    """--dump-outputs: this rank's verdict words of the last timed step, [row][policy], as float64
+    (exact for the 32-bit words). Above DUMP_WORDS / world words a fixed sample of rows, drawn with
+    SEED, is kept; the row numbers (within the rank's shard) go beside it."""
+    import numpy as np
+
+    v = np.asarray(verdicts, dtype=np.uint32)[:nrows * npol].reshape(nrows, npol)
+    keep = max(1, DUMP_WORDS // world // max(npol, 1))
+    if nrows > keep:
+        rows = np.sort(np.random.default_rng(SEED).choice(nrows, size=keep, replace=False))
+    else:
+        rows = np.arange(nrows)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, f"verdicts{suffix}.npy"), v[rows].astype(np.float64))
+    np.save(os.path.join(outdir, f"rows{suffix}.npy"), rows.astype(np.float64))
+    log(f"rank {rank}: wrote {len(rows)} of {nrows} rows x {npol} verdict words to {outdir}")
 
 
 def pcie_rates(nbytes, reps=5):

@@ -4,15 +4,16 @@
 #   CFG=c4_64 DEBUGS="0 1 2 4" bash scripts/ablate_pmc.sh <tag>
 set -u
 ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+OUT=${OUT:-$ROOT/bench_out}; mkdir -p "$OUT"
 TAG=${1:-abl}
 CFG=${CFG:-c4_64}
 cd /tmp && export TMPDIR=/tmp
 ROWS=$(cd "$ROOT" && python3 -c "import bench; print(bench.CONFIGS['$CFG'][1])")
 for d in ${DEBUGS:-0 1 2 4 1024 2048 4096 8192 16384}; do
-  KW_TILE_DEBUG=$d timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --kernel-trace -d "$ROOT/gpurun_out/${TAG}_d$d" -o run --output-format csv -- python3 "$ROOT/bench.py" --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-host-modes > "$ROOT/gpurun_out/${TAG}_d$d.log" 2>&1
+  KW_TILE_DEBUG=$d timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --kernel-trace -d "$OUT/${TAG}_d$d" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-host-modes > "$OUT/${TAG}_d$d.log" 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then echo "[abl] debug=$d exit $rc"; exit $rc; fi
-  (cd "$ROOT" && python3 - "$ROOT/gpurun_out/${TAG}_d$d" "$ROWS" "$d" <<'PY'
+  (cd "$ROOT" && python3 - "$OUT/${TAG}_d$d" "$ROWS" "$d" <<'PY'
 import sys
 sys.path.insert(0, "scripts")
 from pmc_summary import summarise

@@ -4,6 +4,7 @@
 # LDS FIFO and conflict stalls. Two passes (<= 8 SQ counters each), kernel-trace only.
 set -u
 ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
+OUT=${OUT:-$ROOT/bench_out}; mkdir -p "$OUT"
 TAG=${1:-deep}
 CFG=${CFG:-c4_64}
 cd /tmp && export TMPDIR=/tmp
@@ -16,8 +17,8 @@ PASSES=(
 PASSES=("${PASSES[@]:${FIRST:-0}}")
 i=${FIRST:-0}
 for p in "${PASSES[@]}"; do
-  timeout -k 10 -s KILL 200 rocprofv3 --pmc $p --kernel-trace -d "$ROOT/gpurun_out/${TAG}_pmc_$i" -o run --output-format csv -- python3 "$ROOT/bench.py" --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-host-modes > "$ROOT/gpurun_out/${TAG}_pmc_$i.log" 2>&1
-  rc=$?; echo "[deep] pass $i exit $rc"; if [ $rc -ne 0 ]; then tail -3 "$ROOT/gpurun_out/${TAG}_pmc_$i.log"; exit $rc; fi
+  timeout -k 10 -s KILL 200 rocprofv3 --pmc $p --kernel-trace -d "$OUT/${TAG}_pmc_$i" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-host-modes > "$OUT/${TAG}_pmc_$i.log" 2>&1
+  rc=$?; echo "[deep] pass $i exit $rc"; if [ $rc -ne 0 ]; then tail -3 "$OUT/${TAG}_pmc_$i.log"; exit $rc; fi
   i=$((i+1))
 done
-cd "$ROOT" && python3 scripts/pmc_summary.py gpurun_out/${TAG}_pmc_*[0-9]
+cd "$ROOT" && python3 scripts/pmc_summary.py $OUT/${TAG}_pmc_*[0-9]

@@ -2,10 +2,10 @@
 # r06: the default bench line (C4, host modes and CPU baseline included) twice on one box, to put
 # the end-to-end (bulk path) figures next to the pcie rates the same line measures.
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; OUT=${OUT:-$PWD/bench_out}; mkdir -p "$OUT"
 for k in 1 2; do
-  timeout -k 10 400 python bench.py > gpurun_out/r06bt_$k.json 2> gpurun_out/r06bt_$k.err || exit $?
-  python3 - gpurun_out/r06bt_$k.json <<'PY'
+  timeout -k 10 400 python bench.py --full > $OUT/r06bt_$k.json 2> $OUT/r06bt_$k.err || exit $?
+  python3 - $OUT/r06bt_$k.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 t = d["timing_modes"]

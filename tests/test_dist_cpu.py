@@ -145,8 +145,8 @@ def test_job_bounds_weak_and_strong(world):
 def test_bench_multi_gpu_default_is_baselines_strong_job():
     """with WORLD_SIZE > 1 and no size flag, bench.py's `value` is BASELINE's own
     multi-GPU workload — the config's request count as one job sharded across the ranks (strong
-    scaling: C4's 1M over N, C5's 10M) — and weak scaling (that many per rank) is measured beside it
-    as `weak_scaling`. A 2-process gloo dry run (--dry-run: the host walk, 1/1000 of the rows)
+    scaling: C4's 1M over N, C5's 10M) — and with --full weak scaling (that many per rank) is measured
+    beside it as `weak_scaling`. A 2-process gloo dry run (--dry-run: the host walk, 1/1000 of the rows)
     exercises that argument path and prints both fields."""
     import json
     import os
@@ -156,7 +156,7 @@ def test_bench_multi_gpu_default_is_baselines_strong_job():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29561", os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--full"],
                          capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
