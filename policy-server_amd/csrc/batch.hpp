@@ -90,7 +90,7 @@ struct StrCol {
   }
 };
 
-struct DeviceBatch;  // capi.cpp
+struct DeviceBatch;  // devbatch.hpp
 
 // Host copy of a pass's side data (kernels.hpp WideRec): the values of verdict words whose ARG is
 // kArgWide. Filled by kw_batch_verdicts.

@@ -1,19 +1,14 @@
 // capi.cpp — extern "C" implementation of include/kwgpu.h: environment and batch lifetime, HBM
-// residency, planning and launch of the hot path (kernels.hip) and the host epilogue (service.cpp).
+// residency, launch of the hot path (kernels.hip; plan.cpp plans it) and the host epilogue (service.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <functional>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -21,465 +16,18 @@
 #include "../../include/kwgpu.h"
 #include "automaton.hpp"
 #include "batch.hpp"
+#include "devbatch.hpp"
 #include "env.hpp"
 #include "kernels.hpp"
+#include "knobs.hpp"
 #include "metrics.hpp"
+#include "plan.hpp"
+#include "pools.hpp"
 #include "service.hpp"
 #include "slotplan.hpp"
 #include "yaml.hpp"
 
 using namespace kw;
-
-
-struct kw_env {
-  Env e;
-  // identity of this environment for plan caches (an address can be reused by a later one)
-  uint64_t uid = next_uid();
-  static uint64_t next_uid() {
-    static std::atomic<uint64_t> n{1};
-    return n++;
-  }
-};
-
-namespace kw {
-
-// Caching allocators for device memory and pinned host staging: a micro-batch front evaluates
-// thousands of small batches per second, and hipMalloc / hipHostMalloc per batch would dominate.
-// Blocks are kept per (device, size class) up to max_cached() bytes per pool.
-struct BlockPool {
-  bool host;
-  std::mutex m;
-  std::map<std::pair<int, size_t>, std::vector<void*>> free;
-  size_t cached = 0;
-  // cached bytes: device 32 GiB (of 288), pinned host 16 GiB — the bulk path's per-call blocks
-  // (bounce, ring, descriptors) and a re-uploaded batch's image come back from the cache
-  size_t max_cached() const { return host ? (size_t)16 << 30 : (size_t)32 << 30; }
-  explicit BlockPool(bool h) : host(h) {}
-  // size classes: 4 KiB, then eight steps per power of two (<= 12.5 % slack: C5's 3.6 GB image
-  // took a 4 GiB block before)
-  static size_t cls(size_t n) {
-    if (n <= 4096) return 4096;
-    size_t p = 4096;
-    while (p * 2 < n) p <<= 1;  // p < n <= 2p
-    const size_t step = p / 8;
-    return (n + step - 1) / step * step;
-  }
-  hipError_t alloc(int dev, size_t n, void** p) {
-    const size_t c = cls(n);
-    {
-      std::lock_guard<std::mutex> g(m);
-      auto& v = free[{dev, c}];
-      if (!v.empty()) {
-        *p = v.back();
-        v.pop_back();
-        cached -= c;
-        return hipSuccess;
-      }
-    }
-    return host ? hipHostMalloc(p, c, hipHostMallocDefault) : hipMalloc(p, c);
-  }
-  void release(int dev, void* p, size_t n) {
-    if (!p) return;
-    const size_t c = cls(n);
-    std::lock_guard<std::mutex> g(m);
-    if (cached + c > max_cached()) {
-      (void)(host ? hipHostFree(p) : hipFree(p));
-      return;
-    }
-    free[{dev, c}].push_back(p);
-    cached += c;
-  }
-};
-BlockPool& dev_pool() {
-  static BlockPool* p = new BlockPool(false);  // process lifetime (blocks outlive every batch)
-  return *p;
-}
-BlockPool& host_pool() {
-  static BlockPool* p = new BlockPool(true);
-  return *p;
-}
-
-// Non-blocking streams and timing-free events handed back for reuse, per device: creating a
-// stream costs host time on the order of a tenth of a millisecond, and a bulk pass used three.
-// A stream returns here drained (its owner synchronized it). KW_STREAM_POOL=0: A/B knob.
-struct StreamPool {
-  std::mutex m;
-  std::map<int, std::vector<hipStream_t>> streams;
-  std::map<int, std::vector<hipEvent_t>> events;
-  const bool on = !(getenv("KW_STREAM_POOL") && atoi(getenv("KW_STREAM_POOL")) == 0);
-  hipError_t get(int dev, hipStream_t* s) {
-    if (on) {
-      std::lock_guard<std::mutex> g(m);
-      auto& v = streams[dev];
-      if (!v.empty()) {
-        *s = v.back();
-        v.pop_back();
-        return hipSuccess;
-      }
-    }
-    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-  }
-  void put(int dev, hipStream_t s) {
-    if (!s) return;
-    if (!on) {
-      (void)hipStreamDestroy(s);
-      return;
-    }
-    std::lock_guard<std::mutex> g(m);
-    streams[dev].push_back(s);
-  }
-  hipError_t get(int dev, hipEvent_t* e) {
-    if (on) {
-      std::lock_guard<std::mutex> g(m);
-      auto& v = events[dev];
-      if (!v.empty()) {
-        *e = v.back();
-        v.pop_back();
-        return hipSuccess;
-      }
-    }
-    return hipEventCreateWithFlags(e, hipEventDisableTiming);
-  }
-  void put(int dev, hipEvent_t e) {
-    if (!e) return;
-    if (!on) {
-      (void)hipEventDestroy(e);
-      return;
-    }
-    std::lock_guard<std::mutex> g(m);
-    events[dev].push_back(e);
-  }
-};
-StreamPool& stream_pool() {
-  static StreamPool* p = new StreamPool;  // process lifetime, like the block pools
-  return *p;
-}
-
-// Host copy spread over up to 16 threads for large buffers (staging fills and verdict read-back:
-// one thread moves ≈ 10 GB/s, the host's memory system several times that).
-void parallel_copy(void* dst, const void* src, size_t bytes) {
-  constexpr size_t kMin = (size_t)8 << 20;
-  if (bytes < kMin) {
-    memcpy(dst, src, bytes);
-    return;
-  }
-  const size_t nt = std::min<size_t>(16, std::max<size_t>(1, std::min<size_t>(std::thread::hardware_concurrency(), bytes / (kMin / 2))));
-  std::vector<std::thread> th;
-  for (size_t t = 0; t < nt; ++t) {
-    const size_t a = bytes * t / nt, e = bytes * (t + 1) / nt;
-    th.emplace_back([=] { memcpy((uint8_t*)dst + a, (const uint8_t*)src + a, e - a); });
-  }
-  for (auto& x : th) x.join();
-}
-
-// Persistent host workers for the bulk path (kw_validate_host): a parallel-for over many short
-// tasks (copy segments, tile ranges) without starting threads per call. The caller runs tasks too.
-// Each call is a Job on the caller's stack; a worker joins it under the lock (users + 1) and the
-// caller returns only when every task is done and every worker that joined has left, so no worker
-// ever sees another call's counters or a finished call's function.
-class HostWorkers {
- public:
-  static HostWorkers& get() {
-    static HostWorkers* w = new HostWorkers();  // process lifetime (workers park on a condition)
-    return *w;
-  }
-  // fn(i) for every i in [0, n), spread over the workers and the caller; returns when all are done
-  // A single task runs inline on the caller: no lock, no wake-up (kwhost's small micro-batches plan
-  // one tile range per pass, and its pipeline workers must not serialise on run_m_ for that).
-  void run(size_t n, const std::function<void(size_t)>& fn) {
-    if (n == 0) return;
-    if (n == 1) {
-      fn(0);
-      return;
-    }
-    std::lock_guard<std::mutex> one(run_m_);  // one parallel-for at a time
-    Job job;
-    job.fn = &fn;
-    job.n = n;
-    {
-      std::lock_guard<std::mutex> g(m_);
-      job_ = &job;
-      ++gen_;
-    }
-    cv_.notify_all();
-    const size_t mine = job.work();
-    std::unique_lock<std::mutex> g(m_);
-    job_ = nullptr;  // no worker joins after this
-    job.done += mine;
-    done_cv_.wait(g, [&] { return job.done == job.n && job.users == 0; });
-  }
-
- private:
-  struct Job {
-    const std::function<void(size_t)>* fn = nullptr;
-    size_t n = 0;
-    std::atomic<size_t> next{0};
-    size_t done = 0;     // tasks finished (under m_)
-    unsigned users = 0;  // workers inside work() (under m_)
-    size_t work() {
-      size_t k = 0;
-      for (size_t i; (i = next.fetch_add(1)) < n; ++k) (*fn)(i);
-      return k;
-    }
-  };
-  HostWorkers() {
-    const char* e = getenv("KW_HOST_THREADS");
-    unsigned n = e ? (unsigned)std::max(1, atoi(e)) : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    for (unsigned i = 1; i < n; ++i) std::thread([this] { loop(); }).detach();
-  }
-  void loop() {
-    uint64_t seen = 0;
-    for (;;) {
-      Job* j = nullptr;
-      {
-        std::unique_lock<std::mutex> g(m_);
-        cv_.wait(g, [&] { return gen_ != seen && job_ != nullptr; });
-        seen = gen_;
-        j = job_;
-        ++j->users;
-      }
-      const size_t mine = j->work();
-      std::lock_guard<std::mutex> g(m_);
-      j->done += mine;
-      --j->users;
-      if (j->done == j->n && j->users == 0) done_cv_.notify_all();
-    }
-  }
-  std::mutex m_, run_m_;
-  std::condition_variable cv_, done_cv_;
-  Job* job_ = nullptr;
-  uint64_t gen_ = 0;
-};
-
-// Copies of several (dst, src, bytes) segments cut into ~1 MB tasks on the host workers.
-struct CopySeg {
-  void* dst;
-  const void* src;
-  size_t bytes;
-};
-void parallel_copy_segs(const std::vector<CopySeg>& segs) {
-  constexpr size_t kTask = (size_t)1 << 20;
-  std::vector<CopySeg> tasks;
-  for (const CopySeg& c : segs)
-    for (size_t a = 0; a < c.bytes; a += kTask)
-      tasks.push_back({(uint8_t*)c.dst + a, (const uint8_t*)c.src + a, std::min(kTask, c.bytes - a)});
-  HostWorkers::get().run(tasks.size(), [&](size_t i) { memcpy(tasks[i].dst, tasks[i].src, tasks[i].bytes); });
-}
-
-// Requests per tile of the tile kernel forced by KW_SLOT_ROWS (8..255, A/B knob), 0 = chosen per
-// batch (plan_pass: kSlotRows, or taller tiles where they keep enough workgroups per CU).
-// Tile schedule of a launch of `ntiles` tiles over `grid` workgroups: the dynamic one (per-XCD
-// counters, kernels.hip) only where a workgroup runs more than 16 tiles, so that drift between
-// workgroups has room to build up; below that the strided schedule is as balanced and skips the
-// counter traffic: every fetch is an atomic on one L2 line per XCD, serialised — r05 same-box A/B
-// (profiles/r05_sched_ab.txt): strided C4 -2.4 %, C2 -6 %, C1 -40 %, a 64k-request shard -47 %; the
-// dynamic one C5 -7 % (its heavy region), C6 -2 %, C3 -2 %. KW_SCHED=static / dynamic forces one.
-// Tables read from global memory (C6) make tile costs vary with the caches: there the dynamic
-// schedule pays from 4 tiles a workgroup (C6 at 15: -2 %).
-bool sched_dynamic(uint64_t ntiles, uint32_t grid, bool lds_tables) {
-  const char* e = getenv("KW_SCHED");
-  if (e && std::string(e) == "static") return false;
-  if (e && std::string(e) == "dynamic") return true;
-  return ntiles > (lds_tables ? 16ull : 4ull) * std::max<uint32_t>(grid, 1);
-}
-
-// Tile height of a split batch's heavy region (KW_HEAVY_ROWS, A/B knob; 0: planned like any batch).
-uint32_t heavy_rows() {
-  const char* e = getenv("KW_HEAVY_ROWS");
-  const int v = e ? atoi(e) : 0;
-  return (v >= 8 && v <= 255) ? (uint32_t)v : 0u;
-}
-
-uint32_t slot_rows_forced() {
-  const char* e = getenv("KW_SLOT_ROWS");  // read per pass (tests switch it between passes)
-  const int v = e ? atoi(e) : 0;
-  return (v >= 8 && v <= 255) ? (uint32_t)v : 0u;  // tile-local owners are u8
-}
-
-// The next-tile L2 prefetch at run time (KW_L2_PREFETCH=1, A/B knob; the kernel carries its code when
-// built with KW_PREFETCH). Off: running it costs C4 3.5 % and C6 3.8 % (r04 same-box A/B), while the
-// kernel built with the code present and the plan leaving it off was 2 % faster on C2 / C3 / C4
-// than the kernel built without it (profiles/r04_prefetch_ab.txt).
-bool l2_prefetch() {
-  static const bool on = KW_PREFETCH && getenv("KW_L2_PREFETCH") && atoi(getenv("KW_L2_PREFETCH")) != 0;
-  return on;
-}
-
-// Per-tile entity counts and staged byte ranges of a batch, reduced to a high quantile (tile_quantile).
-struct TileStats {
-  uint32_t ctr = 0, lbl = 0, kadd = 0, kdrop = 0;
-  uint32_t bytes[NSTR] = {};
-};
-
-// A split batch's entity maps (upload_batch, permute_batch): the source entity of each destination
-// entity, per level — what the upload gathers the string bytes by (gather_column).
-struct RowOrder {
-  const std::vector<uint64_t>* perm = nullptr;  // rows (DeviceBatch::perm)
-  std::vector<uint32_t> cmap, lmap, amap, dmap;  // containers, labels, added / dropped capabilities
-  uint64_t src(int m, uint64_t e) const {
-    switch (m) {
-      case S_NS: return (*perm)[e];
-      case S_CAPADD: return amap[e];
-      case S_CAPDROP: return dmap[e];
-      case S_LK: case S_LV: return lmap[e];
-      default: return cmap[e];
-    }
-  }
-};
-
-// Device copy of a batch: one allocation for the input columns, lazily sized verdict / plan /
-// side-data buffers, a private stream and timing events.
-struct DeviceBatch {
-  int device = -1;
-  hipStream_t stream = nullptr;  // the batch's stream (passes without a caller stream)
-  bool owns_stream = true;       // false: the caller's stream (kw_batch_to_device_async)
-  void* staging = nullptr;       // pinned host staging of the last upload
-  size_t staging_bytes = 0;
-  hipStream_t cur = nullptr;     // stream of the last pass (kw_batch_verdicts synchronises on it)
-  uint8_t* cols = nullptr;
-  size_t cols_bytes = 0;
-  // device views of the columns
-  const uint8_t* req_flags = nullptr;
-  const uint32_t *ctr_off = nullptr, *lbl_off = nullptr, *capadd_off = nullptr, *capdrop_off = nullptr;
-  const uint8_t* ctr_flags = nullptr;
-  struct DCol {
-    const uint32_t* off = nullptr;
-    const uint8_t* bytes = nullptr;
-    uint64_t n = 0;
-    uint64_t nbytes = 0;
-  } str[NSTR];
-  uint32_t* verdicts = nullptr;
-  size_t verdict_cap = 0;
-  size_t last_verdicts = 0;
-  uint32_t last_row_words = 0;  // verdict words per row of the last pass (npol; rows mode 1)
-  // light / heavy split (upload_batch, split_rows): the device copy holds the batch's rows in
-  // another order — the light rows, then the heavy ones — and every device buffer indexed by row
-  // (verdicts, side data, the rows-mode column map) follows that order; kw_batch_verdicts and
-  // load_side_data scatter them back. perm[d]: the batch row at device row d; split: the light
-  // region's rows (0: not split); dev_b: the reordered batch the planner reads (its offsets only:
-  // the string bytes are dropped after the upload).
-  std::vector<uint64_t> perm;
-  uint64_t split = 0;
-  std::unique_ptr<Batch> dev_b;
-  // the last all-pairs pass's plan (capi.cpp validate_cached; a PassPlan): reused while the
-  // environment, the policy list, the origin and every KW_* setting stay the same — planning a
-  // 64-policy pass is ~60-300 us of host time, the whole GPU time of a small shard
-  std::shared_ptr<void> plan_cache;
-  uint64_t plan_env = 0, plan_knobs = 0;
-  std::vector<int32_t> plan_pols;
-  int plan_origin = -1;
-  std::unique_ptr<RowOrder> order;  // (until the upload's staging is filled)
-  uint32_t loaded = 0;        // string columns (bits of Str) whose bytes are resident (kw_validate_host uploads only its pass's)
-  uint32_t* sched = nullptr;  // tile counters (zeroed once; each launch leaves them zero)
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  // the last pass's plan as the kernels read it (host copies detect a changed plan)
-  TileArgs* d_tiles = nullptr;
-  size_t d_tiles_cap = 0;
-  std::vector<TileArgs> h_tiles;
-  uint8_t* d_slots = nullptr;
-  size_t d_slots_cap = 0;
-  std::vector<uint8_t> h_slots;
-  uint32_t* rowcol = nullptr;
-  size_t rowcol_cap = 0;
-  std::vector<uint32_t> h_rowcol;
-  // host-built tile descriptors + overflow list, cached for one plan geometry (desc_key)
-  TileDesc* desc = nullptr;
-  size_t desc_cap = 0;
-  uint32_t* overflow = nullptr;  // [count, request indices...]
-  size_t overflow_cap = 0;
-  std::vector<TileDesc> h_desc;
-  std::vector<uint32_t> h_ovf;
-  uint32_t n_overflow = 0;
-  uint64_t ndesc = 0;
-  uint64_t reg_desc[2] = {0, 0}, reg_ndesc[2] = {0, 0};  // each region's descriptors within desc
-  uint64_t desc_key = 0;
-  bool desc_valid = false;   // D.desc holds the whole batch's descriptors for desc_key
-  uint32_t needs_stride = 1;  // tile needs sampled every needs_stride-th tile (set by kw_validate_host)
-  // overflow path: per-string classes in HBM (one allocation) and the wide-argument side data
-  uint16_t* g_cls = nullptr;
-  size_t g_cls_cap = 0;
-  // NFA elements: their classes ([label][nlv] | [container][nim]) and the Pike VMs' scratch
-  uint16_t* nfa_cls = nullptr;
-  size_t nfa_cls_cap = 0;
-  uint32_t* nfa_scratch = nullptr;
-  size_t nfa_scratch_cap = 0;
-  uint32_t max_image_len = 0xffffffffu;  // longest image reference of the batch (computed on first use)
-  uint32_t* wide_count = nullptr;
-  bool wide_valid = false;  // the last pass zeroed wide_count and ran the overflow kernels
-  WideRec* wide_rec = nullptr;
-  size_t wide_rec_cap = 0;
-  uint64_t* wide_groups = nullptr;
-  size_t wide_groups_cap = 0;
-  // wide policy groups (WideGroupPass): the members' pass output, the combine kernel's records,
-  // value-stack scratch and the cause bitsets
-  uint32_t* member_words = nullptr;
-  size_t member_words_cap = 0;
-  uint8_t* wg_data = nullptr;
-  size_t wg_data_cap = 0;
-  uint64_t* wg_stack = nullptr;
-  size_t wg_stack_cap = 0;
-  uint64_t* big_causes = nullptr;
-  size_t big_causes_cap = 0;
-  uint32_t last_big_stride = 0;
-  std::vector<WideData::BigRef> last_big_ref;
-  // what the last pass left in the side buffers
-  uint32_t last_nwide = 0, last_wide_cap = 0;
-  bool last_rows_mode = false;
-  std::vector<int32_t> last_wide_policy;
-  // tile capacities of this batch (plan_pass), per tile height tried
-  struct RowsPlan {
-    uint32_t rows = 0;
-    uint64_t lo = 0, hi = 0;         // the region's rows
-    uint32_t stride = 1;            // needs of every stride-th tile (kw_validate_host samples)
-    std::vector<TileStats> need, q;  // per-tile needs and their quantiles
-    uint64_t cap_key = 0;
-    int cap_choice = -1;   // quantile index chosen for cap_key
-    uint32_t cap_cu = 0;   // its workgroups per CU
-    uint32_t cap_lds = 0;  // its LDS bytes
-  };
-  std::deque<RowsPlan> rows_plans;  // deque: plan_rows hands out references that must survive later insertions
-  ~DeviceBatch() {
-    if (device < 0) return;  // host-only view (kw_debug_plan)
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (cur && cur != stream) (void)hipStreamSynchronize(cur);
-    BlockPool& P = dev_pool();
-    P.release(device, d_tiles, d_tiles_cap * sizeof(TileArgs));
-    P.release(device, d_slots, d_slots_cap);
-    P.release(device, rowcol, rowcol_cap * 4);
-    P.release(device, desc, desc_cap * sizeof(TileDesc));
-    P.release(device, overflow, overflow_cap * 4);
-    P.release(device, cols, cols_bytes);
-    P.release(device, verdicts, verdict_cap * 4);
-    P.release(device, g_cls, g_cls_cap * 2);
-    P.release(device, nfa_cls, nfa_cls_cap * 2);
-    P.release(device, nfa_scratch, nfa_scratch_cap * 4);
-    P.release(device, wide_rec, wide_rec_cap * sizeof(WideRec));
-    P.release(device, wide_groups, wide_groups_cap * 8);
-    P.release(device, member_words, member_words_cap * 4);
-    P.release(device, wg_data, wg_data_cap);
-    P.release(device, wg_stack, wg_stack_cap * 8);
-    P.release(device, big_causes, big_causes_cap * 8);
-    P.release(device, sched, 512 * sizeof(uint32_t));  // every launch leaves the tile counters zero
-    P.release(device, wide_count, sizeof(uint32_t));
-    host_pool().release(device, staging, staging_bytes);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (stream && owns_stream) stream_pool().put(device, stream);
-  }
-};
-
-}  // namespace kw
-
-struct kw_batch {
-  Batch b;
-  std::unique_ptr<DeviceBatch> dev;
-  std::vector<void*> host_pinned;  // kw_batch_pin_host: column arrays page-locked in place
-  ~kw_batch() {
-    dev.reset();  // synchronizes the batch's streams: no copy can still read a registered column
-    for (void* p : host_pinned) (void)hipHostUnregister(p);
-  }
-};
 
 namespace {
 
@@ -526,748 +74,6 @@ int upload_env(kw_env* env, int device) {
   HIPCHK(hipMalloc(&env->e.d_blob, env->e.blob.size()));
   HIPCHK(hipMemcpy(env->e.d_blob, env->e.blob.data(), env->e.blob.size(), hipMemcpyHostToDevice));
   env->e.device = device;
-  return KW_OK;
-}
-
-const StrCol& host_str(const Batch& B, int m) {
-  switch (m) {
-    case S_NS: return B.ns;
-    case S_IMG: return B.ctr_image;
-    case S_AA: return B.ctr_aa;
-    case S_CAPADD: return B.cap_add;
-    case S_CAPDROP: return B.cap_drop;
-    case S_LK: return B.lbl_key;
-    default: return B.lbl_val;
-  }
-}
-
-// Entity range [g0, g1) of string column m for requests [r0, r1).
-void str_range(const Batch& B, int m, uint64_t r0, uint64_t r1, uint64_t* g0, uint64_t* g1) {
-  switch (m) {
-    case S_NS: *g0 = r0; *g1 = r1; break;
-    case S_CAPADD: *g0 = B.capadd_off[B.ctr_off[r0]]; *g1 = B.capadd_off[B.ctr_off[r1]]; break;
-    case S_CAPDROP: *g0 = B.capdrop_off[B.ctr_off[r0]]; *g1 = B.capdrop_off[B.ctr_off[r1]]; break;
-    case S_LK: case S_LV: *g0 = B.lbl_off[r0]; *g1 = B.lbl_off[r1]; break;
-    default: *g0 = B.ctr_off[r0]; *g1 = B.ctr_off[r1]; break;
-  }
-}
-
-constexpr uint32_t kTableBudget = 64 * 1024;   // classifiers + chunk records staged per workgroup
-constexpr uint32_t kTileLdsBudget = 160 * 1024;  // tile-kernel LDS per workgroup (gfx950: 160 KB per CU)
-constexpr uint32_t kMaxTileEntities = 60000;    // per-request indices in a tile stay below ARG's 65535
-constexpr double kTileQuantiles[] = {1.0, 0.99995, 0.9999, 0.9995, 0.999, 0.998};  // capacity candidates
-
-// What each tile of `rows` requests of rows [lo, hi) stages: entity counts and the 16-B aligned byte
-// span of each string column.
-std::vector<TileStats> tile_needs(const Batch& B, uint32_t rows, uint32_t stride, uint64_t lo, uint64_t hi) {
-  const uint64_t ntiles_all = (hi - lo + rows - 1) / rows;
-  const uint64_t ntiles = (ntiles_all + stride - 1) / stride;  // sampled tiles: every stride-th
-  std::vector<TileStats> v(ntiles);
-  // tiles in ranges of 256 on the host workers (each tile's reads are cache misses: 1M requests
-  // take ~3 ms on one thread per tile height)
-  constexpr uint64_t kRange = 256;
-  HostWorkers::get().run((size_t)((ntiles + kRange - 1) / kRange), [&](size_t q) {
-  for (uint64_t j = q * kRange, t1 = std::min<uint64_t>(ntiles, (q + 1) * kRange); j < t1; ++j) {
-    const uint64_t t = j * stride;
-    const uint64_t r0 = lo + t * rows, r1 = std::min<uint64_t>(hi, lo + (t + 1) * rows);
-    TileStats& st = v[j];
-    st.ctr = B.ctr_off[r1] - B.ctr_off[r0];
-    st.lbl = B.lbl_off[r1] - B.lbl_off[r0];
-    st.kadd = B.capadd_off[B.ctr_off[r1]] - B.capadd_off[B.ctr_off[r0]];
-    st.kdrop = B.capdrop_off[B.ctr_off[r1]] - B.capdrop_off[B.ctr_off[r0]];
-    for (int m = 0; m < (int)NSTR; ++m) {
-      const StrCol& c = host_str(B, m);
-      uint64_t g0, g1;
-      str_range(B, m, r0, r1, &g0, &g1);
-      st.bytes[m] = ((c.off[g1] + 15u) & ~15u) - (c.off[g0] & ~15u);
-    }
-  }
-  });
-  return v;
-}
-
-// Per-dimension quantile of the tile needs (quantile 1 = the batch maximum).
-TileStats tile_quantile(const std::vector<TileStats>& need, double quantile) {
-  TileStats st;
-  if (need.empty()) return st;
-  const uint64_t n = need.size();
-  const uint64_t q = quantile >= 1.0 ? n - 1 : (uint64_t)(quantile * (double)(n - 1));
-  std::vector<uint32_t> v(n);
-  auto quant = [&](auto f) {
-    for (uint64_t t = 0; t < n; ++t) v[t] = f(need[t]);
-    std::nth_element(v.begin(), v.begin() + (long)q, v.end());
-    return v[q];
-  };
-  st.ctr = quant([](const TileStats& x) { return x.ctr; });
-  st.lbl = quant([](const TileStats& x) { return x.lbl; });
-  st.kadd = quant([](const TileStats& x) { return x.kadd; });
-  st.kdrop = quant([](const TileStats& x) { return x.kdrop; });
-  for (int m = 0; m < (int)NSTR; ++m) st.bytes[m] = quant([m](const TileStats& x) { return x.bytes[m]; });
-  return st;
-}
-
-// All the capacity-candidate quantiles at once (kTileQuantiles order): per dimension one selection
-// at the lowest quantile and a sort of the tail above it (the candidates are all >= 0.998: a few
-// dozen values of a 1M-request batch's 15k tiles), dimensions on the host workers.
-std::vector<TileStats> tile_quantiles(const std::vector<TileStats>& need, const double* qs, size_t nq) {
-  std::vector<TileStats> out(nq);
-  if (need.empty() || nq == 0) return out;
-  const uint64_t n = need.size();
-  std::vector<uint64_t> qi(nq);
-  uint64_t qmin = n - 1;
-  for (size_t k = 0; k < nq; ++k) {
-    qi[k] = qs[k] >= 1.0 ? n - 1 : (uint64_t)(qs[k] * (double)(n - 1));
-    qmin = std::min(qmin, qi[k]);
-  }
-  constexpr int kDims = 4 + (int)NSTR;
-  auto dim = [](const TileStats& x, int d) -> uint32_t {
-    return d == 0 ? x.ctr : d == 1 ? x.lbl : d == 2 ? x.kadd : d == 3 ? x.kdrop : x.bytes[d - 4];
-  };
-  auto put = [](TileStats& x, int d, uint32_t v) {
-    if (d == 0) x.ctr = v;
-    else if (d == 1) x.lbl = v;
-    else if (d == 2) x.kadd = v;
-    else if (d == 3) x.kdrop = v;
-    else x.bytes[d - 4] = v;
-  };
-  auto one_dim = [&](size_t di) {
-    const int d = (int)di;
-    std::vector<uint32_t> v(n);
-    for (uint64_t t = 0; t < n; ++t) v[t] = dim(need[t], d);
-    std::nth_element(v.begin(), v.begin() + (long)qmin, v.end());
-    std::sort(v.begin() + (long)qmin, v.end());
-    for (size_t k = 0; k < qi.size(); ++k) put(out[k], d, v[qi[k]]);
-  };
-  if (n < 8192) {  // a small batch (kwhost's micro-batches): inline, no worker wake-up
-    for (int d = 0; d < kDims; ++d) one_dim((size_t)d);
-  } else {
-    HostWorkers::get().run(kDims, one_dim);
-  }
-  return out;
-}
-
-struct PassPlan {
-  bool rows_mode = false;
-  const uint8_t* env_blob = nullptr;  // host copy of the environment's blob (DevHeader first)
-  NfaPass nfa{};                      // filled by ensure_nfa when the pass has NFA elements
-  uint32_t nfa_threads = 0;
-  std::vector<SlotChunk> chunks;
-  std::vector<std::pair<uint32_t, uint32_t>> launches;  // chunk ranges [first, last)
-  std::vector<TileArgs> tiles;                          // one per launch (record pointers filled at upload)
-  std::vector<uint8_t> slot_blob;                       // the chunks' records, concatenated
-  std::vector<uint32_t> slot_at;                        // offset of each chunk's record in slot_blob
-  TileArgs geom;  // the first region's geometry (the fields every region shares)
-  EvalArgs args;
-  uint32_t grid = 0;
-  // tile geometry per region of the device rows: one, or the light and heavy regions of a split
-  // batch (DeviceBatch::split), each with its own capacities, LDS layout and grid; `tiles` holds
-  // region k's launches at [k * launches.size(), (k + 1) * launches.size())
-  struct Region {
-    uint64_t lo = 0, hi = 0;
-    TileArgs geom;
-    uint32_t grid = 0;
-    bool dyn = true;  // the dynamic tile schedule (sched_dynamic), else the strided one
-  };
-  std::vector<Region> regions;
-  uint32_t nwide = 0;
-  std::vector<int32_t> wide_policy;
-  std::vector<uint32_t> rowcol;  // rows mode
-  uint64_t wide_cap_per_row = 0;
-  double evaluate_bytes = 0;
-  // wide policy groups of the pass (> 64 members or deep stacks): their combine records, jump
-  // code, member slot -> member-pass column maps, the member-pass policy list
-  struct Wide {
-    std::vector<WideGroupArgs> groups;
-    std::vector<int32_t> policy;
-    std::vector<uint8_t> progs;
-    std::vector<uint32_t> midx;
-    std::vector<int32_t> members;
-    // split group members (env.cpp split_policy): records of kind 2 / 3 after the groups' own in
-    // the upload; a member slot's midx entry is kSplitMember | record index
-    std::vector<WideGroupArgs> aux;
-    uint32_t cause_stride = 0, stack_words = 0;
-  } wide;
-};
-
-// The wide groups among the pass's columns (plan->wide): column ids are the output column
-// (all pairs) or the rows-mode column code ((chunk << 16) | column, as rowcol holds).
-void plan_wide_groups(const Env& E, const std::vector<int32_t>& list, const std::vector<uint32_t>* rows_code,
-                      int origin, PassPlan* plan) {
-  PassPlan::Wide& W = plan->wide;
-  W = PassPlan::Wide{};
-  std::map<int32_t, uint32_t> mcol, aux_of;
-  auto member_col = [&](int32_t m) {
-    auto it = mcol.find(m);
-    if (it == mcol.end()) {
-      it = mcol.emplace(m, (uint32_t)W.members.size()).first;
-      W.members.push_back(m);
-    }
-    return it->second;
-  };
-  // a group member that is split: its word is combined from its parts' words where the group
-  // reads it (before, the member pass left a placeholder and the group rejected)
-  auto split_member = [&](int32_t m) -> uint32_t {
-    auto it = aux_of.find(m);
-    if (it != aux_of.end()) return it->second;
-    const PolicyRec& M = E.pol[(size_t)m];
-    WideGroupArgs a;
-    memset(&a, 0, sizeof(a));
-    while (W.progs.size() % 4) W.progs.push_back(0);
-    a.prog_off = (uint32_t)W.progs.size();
-    a.prog_len = (uint32_t)(M.part_off.size() * 4);
-    W.progs.insert(W.progs.end(), (const uint8_t*)M.part_off.data(), (const uint8_t*)(M.part_off.data() + M.part_off.size()));
-    a.kind = M.family == FAM_CAPABILITIES ? 3u : 2u;
-    a.nmem = (uint32_t)M.parts.size();
-    a.okw = finish_word(M.mode, M.allowed_to_mutate, origin, 0, 0, false);
-    a.mutw = finish_word(M.mode, M.allowed_to_mutate, origin, 0, 0, true);
-    a.rejb = finish_word(M.mode, M.allowed_to_mutate, origin, 1, 0, false) & ~0xff00u;
-    std::vector<uint32_t> cols;
-    for (int32_t q : M.parts) cols.push_back(member_col(q));
-    a.midx_off = (uint32_t)W.midx.size();
-    W.midx.insert(W.midx.end(), cols.begin(), cols.end());
-    const uint32_t k = (uint32_t)W.aux.size();
-    W.aux.push_back(a);
-    aux_of.emplace(m, k);
-    return k;
-  };
-  for (uint32_t j = 0; j < (uint32_t)list.size(); ++j) {
-    const PolicyRec& P = E.pol[(size_t)list[j]];
-    const bool split = !P.parts.empty() && !P.init_error;
-    if (!split && (!P.is_group || P.init_error || !P.prog.valid || P.prog.eval_error || !P.prog.wide)) continue;
-    WideGroupArgs g;
-    memset(&g, 0, sizeof(g));
-    while (W.progs.size() % 4) W.progs.push_back(0);
-    g.prog_off = (uint32_t)W.progs.size();
-    if (split) {  // the parts' index offsets (u32 each)
-      g.prog_len = (uint32_t)(P.part_off.size() * 4);
-      W.progs.insert(W.progs.end(), (const uint8_t*)P.part_off.data(), (const uint8_t*)(P.part_off.data() + P.part_off.size()));
-    } else {
-      g.prog_len = (uint32_t)P.prog.code.size();
-      W.progs.insert(W.progs.end(), P.prog.code.begin(), P.prog.code.end());
-    }
-    g.col = rows_code ? (*rows_code)[j] : j;
-    const std::vector<int32_t>& mem = split ? P.parts : P.members;
-    g.nmem = (uint32_t)mem.size();
-    std::vector<uint32_t> cols;
-    for (int32_t m : mem) {
-      const PolicyRec& M = E.pol[(size_t)m];
-      cols.push_back(!split && !M.parts.empty() && !M.init_error ? kSplitMember | split_member(m) : member_col(m));
-    }
-    g.midx_off = (uint32_t)W.midx.size();
-    W.midx.insert(W.midx.end(), cols.begin(), cols.end());
-    if (split) {  // a plain policy's words (slotplan.cpp CK_PLAIN), the reason and argument from its parts
-      g.kind = P.family == FAM_CAPABILITIES ? 3u : 2u;
-      g.okw = finish_word(P.mode, P.allowed_to_mutate, origin, 0, 0, false);
-      g.mutw = finish_word(P.mode, P.allowed_to_mutate, origin, 0, 0, true);
-      g.rejb = finish_word(P.mode, P.allowed_to_mutate, origin, 1, 0, false) & ~0xff00u;
-      g.cause_words = 0;
-    } else {
-      g.okw = finish_word(P.mode, 0, origin, 0, 0, false);
-      g.rejb = finish_word(P.mode, 0, origin, KW_R_GROUP, kArgWide, false);
-      g.errw = finish_word(P.mode, 0, origin, KW_R_GROUP_EXPR, 0, false);
-      g.kind = P.prog.script ? 1u : 0u;
-      g.cause_words = (g.nmem + 63u) / 64u;
-    }
-    // all pairs: every wide column has its own words in a row; rows mode: a row has one column
-    g.cause_off = rows_code ? 0u : W.cause_stride;
-    W.cause_stride = rows_code ? std::max(W.cause_stride, g.cause_words) : W.cause_stride + g.cause_words;
-    if (!split)
-      W.stack_words = std::max<uint32_t>(W.stack_words, P.prog.script ? (uint32_t)run_script_words(P.prog.code.data())
-                                                                       : (P.prog.depth + 63u) / 64u);
-    W.groups.push_back(g);
-    W.policy.push_back(list[j]);
-  }
-}
-
-// The rows the device holds, in device order: the reordered copy of a split batch, else the batch.
-const Batch& dev_rows(const kw_batch* kb) { return kb->dev && kb->dev->dev_b ? *kb->dev->dev_b : kb->b; }
-
-// Plan one pass: slot-plan chunks of the policy list, the launches they take, the tile geometry
-// and LDS layout, the kernel arguments.
-int plan_pass(const kw_env* env, kw_batch* kb, const int32_t* pols, uint32_t npol, const int32_t* row_policy,
-              int origin, PassPlan* plan) {
-  const Env& E = env->e;
-  DeviceBatch& D = *kb->dev;
-  const Batch& B = dev_rows(kb);
-  const DevHeader* H = (const DevHeader*)E.blob.data();
-  plan->env_blob = E.blob.data();
-  plan->rows_mode = row_policy != nullptr;
-  static const bool pdbg = getenv("KW_BULK_DEBUG") && atoi(getenv("KW_BULK_DEBUG")) != 0;  // diagnostics
-  const auto pt0 = std::chrono::steady_clock::now();
-  auto pms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pt0).count(); };
-  // ---- the columns of the pass and their slot-plan chunks
-  std::vector<int32_t> list;
-  std::map<int32_t, uint32_t> col_of;  // rows mode: policy -> column
-  if (plan->rows_mode) {
-    for (uint64_t r = 0; r < B.n; ++r)
-      if (col_of.emplace(row_policy[r], (uint32_t)list.size()).second) list.push_back(row_policy[r]);
-  } else {
-    list.assign(pols, pols + npol);
-  }
-  Status st = build_slot_chunks(E, list.data(), (uint32_t)list.size(), origin, plan->rows_mode, &plan->chunks);
-  if (!st.ok()) return st.code;
-  if (!plan->rows_mode) plan_wide_groups(E, list, nullptr, origin, plan);
-  if (plan->rows_mode) {
-    std::vector<uint32_t> at(list.size());
-    for (uint32_t c = 0; c < plan->chunks.size(); ++c)
-      for (uint32_t j = 0; j < plan->chunks[c].ncols; ++j) at[plan->chunks[c].col0 + j] = (c << 16) | j;
-    plan_wide_groups(E, list, &at, origin, plan);
-    plan->rowcol.resize(B.n);  // (in device-row order)
-    for (uint64_t r = 0; r < B.n; ++r) plan->rowcol[r] = at[col_of[row_policy[D.split ? D.perm[r] : r]]];
-  }
-  plan->nwide = 0;
-  plan->wide_policy.clear();
-  for (const SlotChunk& c : plan->chunks) {
-    const ColInfo* ci = (const ColInfo*)(c.rec.data() + ((const SlotHdr*)c.rec.data())->o_cols);
-    for (uint32_t j = 0; j < c.ncols; ++j)
-      if (ci[j].wide != ~0u) plan->wide_policy.push_back((int32_t)ci[j].policy);
-  }
-  plan->nwide = plan->rows_mode ? (plan->wide_policy.empty() ? 0u : 1u) : (uint32_t)plan->wide_policy.size();
-
-  const double t_slots = pdbg ? pms() : 0.0;
-  // ---- what the chunks classify
-  uint32_t need = 0;
-  bool any_ctr = false, any_caps = false, any_trs = false, any_lbl = false, any_ctr_fam = false;
-  uint32_t nslots = 1;
-  for (const SlotChunk& c : plan->chunks) {
-    const SlotHdr& h = *(const SlotHdr*)c.rec.data();
-    if (h.ns) need |= 1u << S_NS;
-    if (h.trs) need |= 1u << S_IMG, any_trs = true;
-    if (h.aa) need |= 1u << S_AA;
-    if (h.caps) need |= (1u << S_CAPADD) | (1u << S_CAPDROP), any_caps = true;
-    if (h.lbl) {
-      need |= 1u << S_LK;
-      if (H->kv_off) need |= 1u << S_LV;
-      any_lbl = true;
-    }
-    any_ctr = any_ctr || (h.priv[0] | h.priv[1] | h.priv[2] | h.priv[3] | h.caps | h.aa | h.trs) != 0;
-    any_ctr_fam = any_ctr_fam || (h.priv[0] | h.priv[1] | h.priv[2] | h.priv[3] | h.caps | h.aa) != 0;
-    nslots = std::max(nslots, c.nslots);
-  }
-  if (H->bypass_cls) need |= 1u << S_NS;
-  ImgLayout il{0, 0, 0};
-  if (any_trs) {
-    il.nreg = (H->col[COL_REG].lit_off ? 1u : 0u) + H->col[COL_REG].ndfa;
-    il.ntag = (H->col[COL_TAG].lit_off ? 1u : 0u) + H->col[COL_TAG].ndfa;
-    il.nimg = H->col[COL_IMG].ndfa;
-  }
-  const uint32_t nlv = (need & (1u << S_LV)) ? H->col[COL_LV].ndfa : 0u;
-
-  // ---- the classifiers the pass stages: literal tables, DFA chains, the per-key value region
-  struct Stage {
-    uint32_t blob, bytes;
-  };
-  std::vector<Stage> stages;
-  uint32_t lit_of[NCOL] = {}, dfa_of[NCOL] = {};
-  auto stage_col = [&](Col c, bool lit, bool dfa) {
-    const DevCol& dc = H->col[c];
-    if (lit && dc.lit_off) {
-      lit_of[c] = (uint32_t)stages.size() + 1;
-      stages.push_back({dc.lit_off, dc.lit_bytes});
-    }
-    if (dfa && dc.dfa_off) {
-      dfa_of[c] = (uint32_t)stages.size() + 1;
-      stages.push_back({dc.dfa_off, dc.dfa_bytes});
-    }
-  };
-  if (need & (1u << S_NS)) stage_col(COL_NS, true, false);
-  if (need & (1u << S_IMG)) {
-    stage_col(COL_REG, true, true);
-    stage_col(COL_TAG, true, true);
-    stage_col(COL_IMG, false, true);
-  }
-  if (need & (1u << S_AA)) stage_col(COL_AA, true, false);
-  if (need & (1u << S_CAPADD)) stage_col(COL_CAP, true, false);
-  if (need & (1u << S_LK)) stage_col(COL_LK, true, false);
-  uint32_t kv_stage = 0;
-  static const bool kv_global = getenv("KW_KV_GLOBAL") && atoi(getenv("KW_KV_GLOBAL")) != 0;  // A/B knob
-  if ((need & (1u << S_LV)) && !kv_global) {
-    kv_stage = (uint32_t)stages.size() + 1;
-    stages.push_back({H->kv_off, H->kv_bytes});
-  }
-  uint32_t table_bytes = 0;
-  for (const Stage& s : stages) table_bytes += (s.bytes + 15u) & ~15u;
-
-  // ---- launches: chunks grouped so tables + staged records fit the per-workgroup budget; a pass
-  //      whose tables or a single chunk alone exceed it reads them from global memory (L2)
-  bool ldst = table_bytes <= kTableBudget;
-  for (const SlotChunk& c : plan->chunks) ldst = ldst && table_bytes + c.staged <= kTableBudget;
-  if (const char* g = getenv("KW_GLOBAL_TABLES")) ldst = ldst && atoi(g) == 0;  // diagnostics / tests
-  plan->launches.clear();
-  uint32_t area = ldst ? table_bytes : 0;
-  for (uint32_t c = 0; c < plan->chunks.size();) {
-    uint32_t e = c, bytes = 0;
-    while (e < plan->chunks.size() && e - c < kMaxChunks &&
-           (!ldst || table_bytes + bytes + plan->chunks[e].staged <= kTableBudget))
-      bytes += plan->chunks[e++].staged;
-    plan->launches.push_back({c, e});
-    if (ldst) area = std::max(area, table_bytes + bytes);
-    c = e;
-  }
-
-  // ---- tile geometry and LDS layout
-  TileArgs& T = plan->geom;
-  auto align = [](uint32_t x) { return (x + 15u) & ~15u; };
-  uint32_t rows = kSlotRows;  // the tile height the layout below is computed for
-  const uint32_t vw_stride = nslots | 1u;  // odd stride: lanes (requests) spread over the banks
-  const uint32_t nim = il.n();
-  auto layout = [&](const TileStats& ts) -> uint32_t {
-    memset(&T, 0, sizeof(T));
-    double scale = 1.0;
-    for (;;) {
-      const uint32_t cmax = std::min<uint32_t>(kMaxTileEntities, (uint32_t)std::max(1.0, scale * ts.ctr));
-      const uint32_t kmax = std::min<uint32_t>(kMaxTileEntities, (uint32_t)std::max(1.0, scale * std::max(ts.kadd, ts.kdrop)));
-      const uint32_t lmax = std::min<uint32_t>(kMaxTileEntities, (uint32_t)std::max(1.0, scale * ts.lbl));
-      uint32_t off = 16 + align(area);
-      auto take = [&](uint32_t bytes) {
-        const uint32_t o = off;
-        off = align(off + bytes);
-        return o;
-      };
-      T.o_rf = take(rows);
-      T.o_coff = take((rows + 1) * 4);
-      T.o_loff = take((rows + 1) * 4);
-      T.o_cflags = take(cmax + 8);  // staged from the dword holding the first flag
-      T.o_cadd = take((cmax + 1) * 4);
-      T.o_cdrop = take((cmax + 1) * 4);
-      T.o_ns = take(rows * 2);
-      T.o_aa = take((need & (1u << S_AA)) ? cmax * 2 : 0);
-      T.o_img = take((need & (1u << S_IMG)) ? cmax * nim * 2 : 0);
-      T.o_capadd = take(any_caps ? kmax * 2 : 0);
-      T.o_capdrop = take(any_caps ? kmax * 2 : 0);
-      T.o_lk = take(any_lbl ? lmax * 2 : 0);
-      T.o_lv = take(any_lbl ? lmax * nlv * 2 : 0);
-      T.o_vadd = take(any_caps ? kmax * 8 : 0);
-      T.o_vl = take(any_lbl ? lmax * 8 : 0);
-      T.o_vc = take(cmax * 8);
-      T.o_vtr = take(any_trs ? cmax * 8 : 0);
-      T.o_own_c = take(cmax);
-      T.o_own_l = take(lmax);
-      T.o_rej = take(rows * 8);
-      T.o_mut = take(rows * 8);
-      T.o_byp = take(rows);
-      T.o_sa = take(NSTR * 4);
-      T.o_nx = take(16);  // (kernels.hpp TileArgs::o_nx)
-      T.o_desc = take(2 * sizeof(TileDesc));
-      T.o_pf = l2_prefetch() ? take(4 * kPfLanes) : 0u;
-      // union: the staged strings (P0-P1) and the violation words (P2-P3)
-      const uint32_t u0 = off;
-      uint32_t su = u0;
-      for (int m = 0; m < (int)NSTR; ++m) {
-        T.o_so[m] = T.o_sb[m] = T.sb_cap[m] = 0;
-        if (!(need & (1u << m))) continue;
-        const uint32_t cnt = m == S_NS ? rows : (m == S_CAPADD || m == S_CAPDROP) ? kmax : (m == S_LK || m == S_LV) ? lmax : cmax;
-        T.o_so[m] = su;
-        su = align(su + (cnt + 1) * 4);
-        T.sb_cap[m] = align((uint32_t)std::min(16384.0, std::max(16.0, scale * ts.bytes[m])));  // longer tiles split
-        T.o_sb[m] = su;
-        su = align(su + T.sb_cap[m] + 48);  // slack: batched dword reads may run <= 36 bytes past a string start
-      }
-      T.o_vw = u0;
-      T.vw_stride = vw_stride;
-      off = std::max(su, align(u0 + rows * vw_stride * 4));
-      if (off > kTileLdsBudget && scale > 1e-5) {  // capacities shrink until the layout fits; bigger tiles split
-        scale *= 0.8;
-        continue;
-      }
-      T.rows = rows;
-      T.cmax = cmax;
-      T.kmax = kmax;
-      T.lmax = lmax;
-      T.lds_bytes = off;
-      break;
-    }
-    return T.lds_bytes;
-  };
-  auto per_cu = [](uint32_t b) { return std::min<uint32_t>(2048 / kSlotThreads, lds_workgroups_per_cu(b)); };
-  // Capacities at a tile height: the highest occupancy (workgroups per CU, LDS-bound) whose layout
-  // splits at most 2 % of the tiles (a tile beyond the capacities runs as halves, upload_tile_descs),
-  // over per-dimension quantiles of the tile needs; at a given occupancy the largest capacities
-  // (fewest split tiles). Chosen once per batch, tile height and layout signature.
-  const uint64_t key = ((uint64_t)area << 40) ^ ((uint64_t)nslots << 20) ^ ((uint64_t)nim << 12) ^ ((uint64_t)nlv << 8) ^ need;
-  uint64_t rlo = 0, rhi = B.n;  // the region being planned
-  auto plan_rows = [&](uint32_t r) -> DeviceBatch::RowsPlan& {
-    DeviceBatch::RowsPlan* R = nullptr;
-    for (auto& x : D.rows_plans)
-      if (x.rows == r && x.lo == rlo && x.hi == rhi) R = &x;
-    if (!R) {
-      D.rows_plans.emplace_back();
-      R = &D.rows_plans.back();
-      R->rows = r;
-      R->lo = rlo;
-      R->hi = rhi;
-      R->stride = 0;
-    }
-    if (R->stride == 0 || R->stride > D.needs_stride) {  // (a sampled plan is refined when a pass wants every tile)
-      R->stride = std::max<uint32_t>(1, D.needs_stride);
-      R->need = tile_needs(B, r, R->stride, rlo, rhi);
-      R->q = tile_quantiles(R->need, kTileQuantiles, sizeof(kTileQuantiles) / sizeof(kTileQuantiles[0]));
-      R->cap_choice = -1;
-    }
-    rows = r;
-    if (R->cap_choice < 0 || R->cap_key != key) {
-      const uint64_t ntl = R->need.size();
-      int best = 0;
-      uint32_t best_cu = 0, best_lds = 0;
-      const double max_split = getenv("KW_TILE_SPLIT") ? atof(getenv("KW_TILE_SPLIT")) : 0.02;  // A/B knob
-      for (int k = 0; k < (int)R->q.size(); ++k) {
-        const uint32_t cu = per_cu(layout(R->q[k]));
-        if (T.lds_bytes > kTileLdsBudget) continue;
-        uint64_t over = 0;  // tiles beyond these capacities (split by the descriptors' fit test)
-        for (const TileStats& x : R->need) {
-          bool o = x.ctr > T.cmax || x.lbl > T.lmax || x.kadd > T.kmax || x.kdrop > T.kmax;
-          for (int m = 0; m < (int)NSTR && !o; ++m) o = T.sb_cap[m] && x.bytes[m] > T.sb_cap[m];
-          over += o;
-        }
-        if (getenv("KW_TILE_DEBUG") && (atoi(getenv("KW_TILE_DEBUG")) & 256))
-          fprintf(stderr, "[kw tile] rows=%u candidate q=%g lds=%u wg/cu=%u split=%llu/%llu\n", r, kTileQuantiles[k], T.lds_bytes, cu,
-                  (unsigned long long)over, (unsigned long long)ntl);
-        if (k > 0 && (double)over > max_split * (double)ntl) continue;
-        if (cu > best_cu) {
-          best = k;
-          best_cu = cu;
-          best_lds = T.lds_bytes;
-        }
-      }
-      R->cap_key = key;
-      R->cap_choice = best;
-      R->cap_cu = best_cu;
-      R->cap_lds = best_lds;
-    }
-    return *R;
-  };
-  // Tile height: KW_SLOT_ROWS when forced; else kSlotRows, or a taller tile (128 down to 96 rows)
-  // when the batch has at least 4 tiles per workgroup slot, the taller layout still keeps 4
-  // workgroups per CU (its LDS estimated from the 64-row layout first: the per-request part scales
-  // with the height), and at most KW_ROUND_SPLIT (2 %) of its tiles hold more items in one P1
-  // segment (labels, capability strings, containers / images) than the workgroup has lanes: such a
-  // tile sends one wave through the segment twice, and its phase waits for that wave (r03: half of
-  // C2 / C3's 128-row tiles had more than 256 images). Taller tiles amortise the per-tile latency
-  // (staging, barriers) where the per-request LDS is small: C2 -12 %, C3 -25 % at 128 rows (r02);
-  // the C4-C6 layouts need 64 rows for 4 workgroups per CU (r02 sweeps). Per region: a split
-  // batch's light region takes the capacities (and occupancy) of its own tiles.
-  std::vector<std::pair<uint64_t, uint64_t>> bounds{{0, B.n}};
-  if (D.split && D.split < B.n) bounds = {{0, D.split}, {D.split, B.n}};
-  plan->regions.clear();
-  for (const auto& [lo, hi] : bounds) {
-  rlo = lo;
-  rhi = hi;
-  const DeviceBatch::RowsPlan* pick = nullptr;
-  const double round_split = getenv("KW_ROUND_SPLIT") ? atof(getenv("KW_ROUND_SPLIT")) : 0.02;  // A/B knob
-  auto two_rounds = [&](const DeviceBatch::RowsPlan& R) {  // share of tiles with a segment beyond one round
-    uint64_t over = 0;
-    for (const TileStats& x : R.need) {
-      uint32_t seg = 0;
-      if (any_lbl) seg = std::max(seg, x.lbl);
-      if (any_caps) seg = std::max(seg, x.kadd + x.kdrop);
-      if (any_ctr || (need & (1u << S_IMG))) seg = std::max(seg, x.ctr);
-      over += seg > kSlotThreads;
-    }
-    return R.need.empty() ? 0.0 : (double)over / (double)R.need.size();
-  };
-  if (const uint32_t f = slot_rows_forced()) {
-    pick = &plan_rows(f);
-  } else if (lo > 0) {
-    // the heavy region of a split batch: the tallest tile height whose capacities reach the
-    // kernel's register-bound occupancy (<= 128 VGPRs: 4 workgroups of 256 threads per CU), else
-    // the one with the most workgroups per CU. r05 C5 sweep (profiles/r05_split_ab.txt): at equal
-    // occupancy taller tiles win (heavy > 5: 12 rows 6.31 ms, 10 rows 6.85), and a layout one
-    // workgroup per CU short loses 10-15 % whatever its height.
-    if (const uint32_t h = heavy_rows()) {
-      pick = &plan_rows(h);
-    } else {
-      for (uint32_t r : {64u, 48u, 40u, 32u, 28u, 24u, 20u, 16u, 14u, 12u, 10u, 8u}) {
-        const DeviceBatch::RowsPlan& R = plan_rows(r);
-        if (!pick || R.cap_cu > pick->cap_cu) pick = &R;
-        if (R.cap_cu >= 4) break;
-      }
-    }
-  } else {
-    const DeviceBatch::RowsPlan& base = plan_rows(kSlotRows);
-    pick = &base;
-    const uint32_t fixed = 16 + align(area), per64 = base.cap_lds > fixed ? base.cap_lds - fixed : 0u;
-    for (uint32_t r : {128u, 120u, 112u, 104u, 96u}) {
-      const uint64_t est = fixed + (uint64_t)per64 * r / kSlotRows;
-      if (getenv("KW_TILE_DEBUG") && (atoi(getenv("KW_TILE_DEBUG")) & 256))
-        fprintf(stderr, "[kw tile] rows=%u estimated lds=%llu (64-row layout %u, fixed %u) region rows %llu\n", r,
-                (unsigned long long)est, base.cap_lds, fixed, (unsigned long long)(rhi - rlo));
-      if (per_cu((uint32_t)std::min<uint64_t>(est, 1u << 30)) < 4 || rhi - rlo < (uint64_t)r * 4 * 256 * 4) continue;
-      const DeviceBatch::RowsPlan& R = plan_rows(r);
-      const double tr = two_rounds(R);
-      if (getenv("KW_TILE_DEBUG") && (atoi(getenv("KW_TILE_DEBUG")) & 256))
-        fprintf(stderr, "[kw tile] rows=%u workgroups/CU %u, tiles with a segment beyond %u items %.4f\n", r, R.cap_cu,
-                kSlotThreads, tr);
-      if (R.cap_cu >= 4 && tr <= round_split) {
-        pick = &R;
-        break;
-      }
-    }
-  }
-  rows = pick->rows;
-  if (pdbg) fprintf(stderr, "[kw plan] slot chunks %.2f ms, tile needs + capacities %.2f ms\n", t_slots, pms() - t_slots);
-  if (const char* fq = getenv("KW_TILE_QUANTILE"))  // tests / diagnostics: force the capacity quantile
-    layout(tile_quantile(pick->need, atof(fq)));
-  else
-    layout(pick->q[pick->cap_choice]);
-  if (T.lds_bytes > kTileLdsBudget) return KW_E_ARG;  // policy list too large for one tile
-  // next-tile L2 prefetch (compiled in with KW_PREFETCH, kernels.hpp): a gain where several small
-  // tiles share a CU, a loss where two large ones do (C5: +2.7 %; r02 A/B); off by default since the
-  // descriptor moved to LDS (r02 s60)
-  T.prefetch = l2_prefetch() && per_cu(T.lds_bytes) >= 3 ? 1u : 0u;
-  // predecessor ranges four loads a round where tiles hold many containers per request (C5 -6 %;
-  // C4, two per request, keeps the plain loops: r02 s80)
-  T.ctr_ranges = T.cmax > 4u * T.rows ? 1u : 0u;
-  PassPlan::Region g;
-  g.lo = lo;
-  g.hi = hi;
-  g.geom = T;
-  const uint64_t nt = (hi - lo + T.rows - 1) / T.rows;
-  g.grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nt, 256ull * per_cu(T.lds_bytes)));
-  g.dyn = sched_dynamic(nt, g.grid, ldst);
-  plan->regions.push_back(g);
-  }
-  bool any_grp = false;
-  for (const SlotChunk& c : plan->chunks) any_grp = any_grp || c.groups;
-  // the fields every region shares
-  for (PassPlan::Region& rg : plan->regions) {
-  T = rg.geom;
-  T.feat = ((need & (1u << S_IMG)) ? kFeatImg : 0u) | (any_lbl ? kFeatLbl : 0u) | (any_ctr_fam ? kFeatCtr : 0u) |
-           (any_grp ? kFeatGrp : 0u);
-  // NFA elements among the classifiers the pass reads: the one instantiation that reads their classes
-  const bool nfa_img = (need & (1u << S_IMG)) &&
-                       ((H->col[COL_REG].flags | H->col[COL_TAG].flags | H->col[COL_IMG].flags) & 1u);
-  const bool nfa_lv = (need & (1u << S_LV)) && (H->col[COL_LV].flags & 1u);
-  if (nfa_img || nfa_lv) T.feat = kFeatAll | kFeatNfa;
-  // many containers per request (C5's heavy region): the wave-scan instantiation (kernels.hpp kFeatRng)
-  if (T.ctr_ranges && ldst && T.feat == (kFeatLbl | kFeatCtr)) T.feat |= kFeatRng;
-  T.il = il;
-  T.nlv = nlv;
-  T.need = need;
-  T.lds_tables = ldst ? 1u : 0u;
-  T.nlk = H->col[COL_LK].nclass;
-  T.bypass_cls = H->bypass_cls;
-  T.docker_io_cls = H->docker_io_cls;
-  T.latest_cls = H->latest_cls;
-  T.rows_mode = plan->rows_mode ? 1u : 0u;
-  for (int m = 0; m < (int)NSTR; ++m) {
-    T.s_off[m] = D.str[m].off;
-    T.s_bytes[m] = D.str[m].bytes;
-  }
-  // classifiers: blob offsets, and their LDS positions when staged
-  {
-    uint32_t at = 16;
-    std::vector<uint32_t> lds_at(stages.size());
-    for (size_t k = 0; k < stages.size(); ++k) {
-      lds_at[k] = at;
-      at += (stages[k].bytes + 15u) & ~15u;
-    }
-    T.nstage = 0;
-    if (ldst)
-      for (size_t k = 0; k < stages.size(); ++k) {
-        T.stage_blob[T.nstage] = stages[k].blob;
-        T.stage_lds[T.nstage] = lds_at[k];
-        T.stage_bytes[T.nstage] = (stages[k].bytes + 15u) & ~15u;
-        ++T.nstage;
-      }
-    for (int c = 0; c < (int)NCOL; ++c) {
-      if (lit_of[c]) {
-        T.lit_blob[c] = stages[lit_of[c] - 1].blob;
-        T.lit_lds[c] = lds_at[lit_of[c] - 1];
-      }
-      if (dfa_of[c]) {
-        T.dfa_blob[c] = stages[dfa_of[c] - 1].blob;
-        T.dfa_lds[c] = lds_at[dfa_of[c] - 1];
-      }
-    }
-    if (kv_stage) {
-      T.kv_blob = stages[kv_stage - 1].blob;
-      T.kv_lds = ldst ? lds_at[kv_stage - 1] : 0u;
-    } else if (need & (1u << S_LV)) {  // the value DFAs read from the blob (global memory, L1/L2)
-      T.kv_blob = H->kv_off;
-      T.kv_lds = 0;
-    }
-  }
-  if (const char* dbg = getenv("KW_TILE_DEBUG")) T.debug = (uint32_t)atoi(dbg);  // phase ablation (diagnostics)
-  if (T.debug & 256u)
-    fprintf(stderr, "[kw tile] lds_tables=%u rows=%u cmax=%u kmax=%u lmax=%u lds=%u area=%u (classifiers %u) chunks=%zu launches=%zu nim=%u nlv=%u\n",
-            T.lds_tables, T.rows, T.cmax, T.kmax, T.lmax, T.lds_bytes, area, table_bytes, plan->chunks.size(), plan->launches.size(), nim,
-            nlv);
-  if (T.debug & 256u) {
-    for (size_t k = 0; k < stages.size(); ++k) fprintf(stderr, "[kw tile]   classifier stage %zu: %u bytes\n", k, stages[k].bytes);
-    // the tile's LDS regions (bytes): per-request state, entity classes and sets, the strings / violation-words union
-    uint32_t so = 0, sb = 0;
-    for (int m = 0; m < (int)NSTR; ++m)
-      if (T.o_sb[m]) so += T.o_sb[m] - T.o_so[m], sb += T.sb_cap[m] + 48;
-    fprintf(stderr,
-            "[kw tile]   layout: headers %u | classes ns %u aa %u img %u caps %u lk %u lv %u | sets vadd %u vl %u vc %u vtr %u | "
-            "owners %u | rej/mut/byp %u | union at %u: string offsets %u + bytes %u, violation words %u | total %u\n",
-            T.o_ns - T.o_rf, T.o_aa - T.o_ns, T.o_img - T.o_aa, T.o_capadd - T.o_img, T.o_lk - T.o_capadd, T.o_lv - T.o_lk,
-            T.o_vadd - T.o_lv, T.o_vl - T.o_vadd, T.o_vc - T.o_vl, T.o_vtr - T.o_vc, T.o_own_c - T.o_vtr, T.o_rej - T.o_own_c,
-            T.o_sa - T.o_rej, T.o_vw, so, sb, T.rows * T.vw_stride * 4, T.lds_bytes);
-  }
-  rg.geom = T;
-  }
-  T = plan->regions[0].geom;
-
-  // ---- per-launch TileArgs (record pointers filled in at upload, run_pass), region by region
-  plan->slot_blob.clear();
-  plan->slot_at.clear();
-  for (const SlotChunk& c : plan->chunks) {
-    plan->slot_at.push_back((uint32_t)plan->slot_blob.size());
-    plan->slot_blob.insert(plan->slot_blob.end(), c.rec.begin(), c.rec.end());
-  }
-  plan->tiles.clear();
-  for (const PassPlan::Region& rg : plan->regions)
-  for (const auto& [c0, c1] : plan->launches) {
-    TileArgs t = rg.geom;
-    t.nchunk = c1 - c0;
-    uint32_t at = 16 + table_bytes;
-    for (uint32_t k = 0; k < t.nchunk; ++k) {
-      const SlotChunk& c = plan->chunks[c0 + k];
-      ChunkArgs& ca = t.chunk[k];
-      memset(&ca, 0, sizeof(ca));
-      ca.o_lds = ldst ? at : 0u;
-      at += c.staged;
-      ca.col0 = c.col0;
-      ca.ncols = c.ncols;
-      ca.vec4 = (!plan->rows_mode && npol % 4u == 0 && c.col0 % 4u == 0 && c.ncols % 4u == 0) ? 1u : 0u;
-      ca.init = ((const SlotHdr*)c.rec.data())->init;
-    }
-    plan->tiles.push_back(t);
-  }
-
-  // ---- evaluation arguments
-  EvalArgs& A = plan->args;
-  memset(&A, 0, sizeof(A));
-  A.blob = (const uint8_t*)E.d_blob;
-  A.nrows = B.n;
-  A.npol = plan->rows_mode ? 1u : npol;
-  A.origin = origin;
-  A.req_flags = D.req_flags;
-  A.ctr_off = D.ctr_off;
-  A.lbl_off = D.lbl_off;
-  A.ctr_flags = D.ctr_flags;
-  A.capadd_off = D.capadd_off;
-  A.capdrop_off = D.capdrop_off;
-  A.out = D.verdicts;
-  A.nwide = plan->nwide;
-  plan->wide_cap_per_row = plan->rows_mode ? 1u : npol;
-  // every column the kernel dereferences must be present (a null column is a device fault)
-  if (!A.req_flags || !A.ctr_off || !A.lbl_off || !A.ctr_flags || !A.capadd_off || !A.capdrop_off || !A.out) return KW_E_ARG;
-  for (int m = 0; m < (int)NSTR; ++m)
-    if ((need & (1u << m)) && (!T.s_off[m] || !T.s_bytes[m])) return KW_E_ARG;
-
-  // algorithmic bytes: request headers once, the entity columns and strings the policies read, and
-  // the verdict words written
-  const double n = (double)B.n;
-  double eb = n * (1 + 4 + 4) + 4.0 * n * (double)A.npol;
-  if (any_ctr) eb += (double)B.containers() * 1.0;
-  if (any_caps) eb += (double)B.containers() * 8.0;
-  for (int m = 0; m < (int)NSTR; ++m)
-    if (need & (1u << m)) eb += (double)D.str[m].nbytes + 4.0 * (double)D.str[m].n;
-  plan->evaluate_bytes = eb;
-
-  plan->grid = plan->regions[0].grid;
   return KW_OK;
 }
 
@@ -1358,7 +164,7 @@ int upload_tile_descs(const Batch& B, DeviceBatch* D, const PassPlan& plan, hipS
     }
   }
   if (D->desc && D->desc_valid && key == D->desc_key) return KW_OK;
-  static const bool dbg = getenv("KW_BULK_DEBUG") && atoi(getenv("KW_BULK_DEBUG")) != 0;  // diagnostics
+  const bool dbg = Knobs::on<KW_BULK_DEBUG>();  // diagnostics
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<TileDesc> desc;
   std::vector<uint32_t> ovf{0};
@@ -1505,7 +311,7 @@ int prepare_pass(kw_batch* kb, PassPlan& plan, hipStream_t s, EvalArgs* out_args
   // tests: KW_POISON_VERDICTS fills the verdict words with a sentinel no verdict word equals
   // (reason byte 0xA5) before the pass, so a tile the schedule never ran shows up as a mismatch
   // instead of keeping an earlier pass's words
-  if (const char* pz = getenv("KW_POISON_VERDICTS"); pz && atoi(pz) != 0)
+  if (Knobs::on<KW_POISON_VERDICTS>())
     HIPCHK(hipMemsetAsync(D.verdicts, 0xA5, D.last_verdicts * sizeof(uint32_t), s));
   // the dynamic tile schedule's per-XCD counters (used by the regions whose plan says so,
   // sched_dynamic; run_pass hands them to those launches only)
@@ -1640,7 +446,7 @@ int run_validate(const kw_env* env, kw_batch* kb, PassPlan& plan, int origin, bo
   if (int rc = ensure(&D.member_words, &D.member_words_cap, (size_t)(n * nm))) return rc;
   {
     PassPlan mplan;
-    if (int rc = plan_pass(env, kb, W.members.data(), (uint32_t)nm, nullptr, origin, &mplan)) return rc;
+    if (int rc = plan_pass(env, kb, W.members.data(), (uint32_t)nm, nullptr, origin, Knobs::on<KW_BULK_DEBUG>(), &mplan)) return rc;
     mplan.args.out = D.member_words;
     if (int rc = run_pass(kb, mplan, false, s)) return rc;
   }
@@ -1690,23 +496,6 @@ int run_validate(const kw_env* env, kw_batch* kb, PassPlan& plan, int origin, bo
   return KW_OK;
 }
 
-// The plan cache's key for the diagnostic / A-B settings (tests switch them between passes): the
-// values of exactly the KW_* variables that planning reads (plan_pass and the planners it calls),
-// looked up by name — no walk over `environ`, which a concurrent setenv could free under it.
-uint64_t kw_knob_hash() {
-  static const char* const kPlanKnobs[] = {"KW_TILE_DEBUG", "KW_TILE_SPLIT", "KW_ROUND_SPLIT", "KW_L2_PREFETCH",
-                                           "KW_KV_GLOBAL", "KW_TILE_QUANTILE", "KW_SPLIT", "KW_SLOT_ROWS",
-                                           "KW_SCHED", "KW_HEAVY_ROWS", "KW_HEAVY_CTR", "KW_GLOBAL_TABLES",
-                                           "KW_NO_MPACK", "KW_POISON_VERDICTS", "KW_GROUP_FORM"};
-  uint64_t h = 1469598103934665603ull;
-  for (const char* k : kPlanKnobs) {
-    const char* v = getenv(k);
-    h = (h ^ (v ? 0x100u : 0x200u)) * 1099511628211ull;
-    for (const char* c = v; c && *c; ++c) h = (h ^ (uint8_t)*c) * 1099511628211ull;
-  }
-  return h;
-}
-
 int validate_common(const kw_env* env, kw_batch* kb, const int32_t* policies, uint32_t npol, const int32_t* row_policy,
                     int origin, PassPlan* plan) {
   if (!env || !kb) return KW_E_ARG;
@@ -1732,7 +521,7 @@ int validate_common(const kw_env* env, kw_batch* kb, const int32_t* policies, ui
   if (int rc = ensure(&D.verdicts, &D.verdict_cap, npairs)) return rc;
   D.last_verdicts = npairs;
   kb->b.wide.clear();
-  if (int rc = plan_pass(env, kb, policies, npol, row_policy, origin, plan)) return rc;
+  if (int rc = plan_pass(env, kb, policies, npol, row_policy, origin, Knobs::on<KW_BULK_DEBUG>(), plan)) return rc;
   return (plan->geom.need & ~D.loaded) ? KW_E_ARG : KW_OK;  // a column the upload left out (kw_validate_host)
 }
 
@@ -1744,7 +533,7 @@ int validate_cached(const kw_env* env, kw_batch* kb, const int32_t* policies, ui
   const uint64_t knobs = kw_knob_hash();
   if (env && D && D->plan_cache && D->plan_env == env->uid && D->plan_origin == origin && D->plan_knobs == knobs &&
       D->plan_pols.size() == npol && policies && std::equal(policies, policies + npol, D->plan_pols.begin())) {
-    PassPlan* plan = (PassPlan*)D->plan_cache.get();
+    PassPlan* plan = D->plan_cache.get();
     const Env& E = env->e;
     if (E.device < 0 || !E.d_blob) return KW_E_DEVICE;
     if (D->device != E.device) return KW_E_ARG;
@@ -2160,7 +949,7 @@ int kw_batch_from_json(const char* const* docs, const size_t* lens, size_t n, in
   // contiguous document ranges flattened by up to KW_FLATTEN_THREADS threads (default: the
   // hardware threads, at most 16), then concatenated in order; the first bad row wins
   uint32_t nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (const char* t = getenv("KW_FLATTEN_THREADS")) nt = (uint32_t)std::max(1, atoi(t));
+  if (const int t = Knobs::num<KW_FLATTEN_THREADS>()) nt = (uint32_t)t;
   nt = (uint32_t)std::min<uint64_t>(nt, std::max<size_t>(1, n / 2048));
   std::vector<Batch> part(nt);
   std::vector<int64_t> bad(nt, -1);
@@ -2238,10 +1027,9 @@ struct Piece {
 // ---- light / heavy split at upload. A batch whose container counts
 // are heavy-tailed (C5: Zipf over 1..64 — 14.7 % of the requests hold 63 % of the containers) sizes
 // every tile's capacities, and so the occupancy, by the heavy requests scattered through it. The
-// device copy instead holds the light requests (<= kHeavyCtr containers) first and the heavy ones
-// after them, in batch order within each region; the planner gives each region its own tile
-// geometry (plan_pass), and verdicts and side data are scattered back to batch rows on the host.
-constexpr uint32_t kHeavyCtr = 5;
+// device copy instead holds the light requests (<= KW_HEAVY_CTR containers, 5) first and the heavy
+// ones after them, in batch order within each region; the planner gives each region its own tile
+// geometry (plan.cpp plan_pass), and verdicts and side data are scattered back to batch rows on the host.
 constexpr uint64_t kSplitMinRows = 1ull << 18;
 
 // The light region's row count and the device-row order (perm[d] = batch row), or 0 when the batch
@@ -2249,11 +1037,9 @@ constexpr uint64_t kSplitMinRows = 1ull << 18;
 // the containers, in a batch of at least kSplitMinRows rows. KW_SPLIT=0 never splits, KW_SPLIT=1
 // splits whenever both regions are non-empty (tests).
 uint64_t split_rows(const Batch& B, std::vector<uint64_t>* perm) {
-  const char* env = getenv("KW_SPLIT");
-  const int mode = env ? atoi(env) : -1;
+  const int mode = Knobs::num<KW_SPLIT>();
   if (mode == 0 || B.n == 0) return 0;
-  const char* hc = getenv("KW_HEAVY_CTR");  // A/B knob: the container count above which a request is heavy
-  const uint32_t thr = hc && atoi(hc) > 0 ? (uint32_t)atoi(hc) : kHeavyCtr;
+  const uint32_t thr = (uint32_t)Knobs::num<KW_HEAVY_CTR>();  // A/B knob: the container count above which a request is heavy
   auto heavy = [&](uint64_t r) { return B.ctr_off[r + 1] - B.ctr_off[r] > thr; };
   uint64_t nh = 0, ch = 0;
   for (uint64_t r = 0; r < B.n; ++r)
@@ -2539,7 +1325,7 @@ int validate_host(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
   if (env->e.device < 0 || !env->e.d_blob) return KW_E_DEVICE;
   if (device != env->e.device || count != kb->b.n * (uint64_t)npol) return KW_E_ARG;
   // diagnostics (KW_BULK_DEBUG=1): host wall time of each stage, printed at the end
-  static const bool dbg = getenv("KW_BULK_DEBUG") && atoi(getenv("KW_BULK_DEBUG")) != 0;
+  const bool dbg = Knobs::on<KW_BULK_DEBUG>();
   using clk = std::chrono::steady_clock;
   const auto t_start = clk::now();
   double t_layout = 0, t_plan = 0, t_prep = 0, t_desc = 0, t_fill = 0, t_enq = 0, t_out = 0, t_first = -1;
@@ -2551,7 +1337,7 @@ int validate_host(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
   const Batch& B = kb->b;
   D.loaded = ~0u;  // (planned as if resident; set to the pass's columns below)
   // tile capacities from about 2048 sampled tiles (KW_BULK_SAMPLE=0: every tile, A/B knob)
-  static const bool sample = !(getenv("KW_BULK_SAMPLE") && atoi(getenv("KW_BULK_SAMPLE")) == 0);
+  const bool sample = Knobs::on<KW_BULK_SAMPLE>();
   D.needs_stride = sample ? (uint32_t)std::max<uint64_t>(1, B.n / ((uint64_t)kSlotRows * 2048)) : 1u;
   PassPlan plan;
   const int prc = validate_common(env, kb, policies, npol, nullptr, origin, &plan);
@@ -2580,7 +1366,7 @@ int validate_host(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
                        !(plan.geom.debug & 512u) && !(plan.geom.feat & kFeatNfa) && B.n > 0;
   // the staging image of the whole batch only where it is used: the unchunked path and per-range
   // copies (packed chunks go through their own ring; pinning C5's 3.6 GB image cost 360 ms a call)
-  static const bool pack_knob = !(getenv("KW_BULK_PACK") && atoi(getenv("KW_BULK_PACK")) == 0);
+  const bool pack_knob = Knobs::on<KW_BULK_PACK>();
   if ((!chunked || !pack_knob) && !D.staging) {
     HIPCHK(host_pool().alloc(device, D.cols_bytes, &D.staging));
     D.staging_bytes = D.cols_bytes;
@@ -2609,12 +1395,12 @@ int validate_host(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
   D.loaded = need;
   const TileArgs& G = plan.geom;
   const uint64_t ntiles = (B.n + G.rows - 1) / G.rows;
-  static const uint64_t def_chunk = getenv("KW_BULK_CHUNK") ? std::max(1, atoi(getenv("KW_BULK_CHUNK"))) : 262144;  // A/B knob (profiles/r04_bulk_sweep.txt)
+  const uint64_t def_chunk = (uint64_t)Knobs::num<KW_BULK_CHUNK>();  // A/B knob (profiles/r04_bulk_sweep.txt)
   const uint64_t per = chunk_rows ? chunk_rows : def_chunk;
   // chunk k: tiles [tb[k], tb[k+1]). The read-back stream is the longest (4 B x npol per request
   // out vs the request's columns in), so the first chunks are small (1/16 of `per`, doubling) to
   // start it early; then `per` rows a chunk.
-  static const bool ramp = !(getenv("KW_BULK_RAMP") && atoi(getenv("KW_BULK_RAMP")) == 0);  // A/B knob
+  const bool ramp = Knobs::on<KW_BULK_RAMP>();  // A/B knob
   // The last chunks shrink the same way (r05): the final chunk's read-back overlaps nothing, so a
   // full-size last chunk left ~1 ms of C4's read-back exposed. At most ~240 chunks (per grows).
   const uint64_t tper = std::max<uint64_t>({1, per / G.rows, (ntiles + 239) / 240});
@@ -2637,7 +1423,7 @@ int validate_host(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
   const uint64_t K = tb.size() - 1;
   auto row_of = [&](uint64_t t) { return std::min<uint64_t>(B.n, t * G.rows); };
   hipPointerAttribute_t attr;
-  static const bool direct = !(getenv("KW_BULK_DIRECT") && atoi(getenv("KW_BULK_DIRECT")) == 0);  // A/B knob
+  const bool direct = Knobs::on<KW_BULK_DIRECT>();  // A/B knob
   const bool pinned = direct && hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeHost;
   (void)hipGetLastError();  // a pageable pointer leaves an error state behind
   // pinned output: at most `depth` chunks in flight past the read-back. Unbounded, the host queues
@@ -2645,7 +1431,7 @@ int validate_host(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
   // 9.7-10.9 at depth 2, profiles/r04_bulk_modes.txt). Staged columns take 3 (the host fills pace
   // the uploads), columns DMA'd in place 2 (at 3 their uploads crowd the read-backs: 11.0 vs
   // 7.1 ms, profiles/r04_bulk_sweep.txt). KW_BULK_DEPTH: A/B knob, 0 = unbounded.
-  static const int depth_knob = getenv("KW_BULK_DEPTH") ? std::max(0, atoi(getenv("KW_BULK_DEPTH"))) : -1;
+  const int depth_knob = Knobs::num<KW_BULK_DEPTH>();
   const bool any_dma = std::count(dma.begin(), dma.end(), 1) > 0;
   const uint64_t depth = depth_knob >= 0 ? (uint64_t)depth_knob : (any_dma ? 2 : 3);
   // (the largest chunk: `per` grows past ~240 chunks)
@@ -3015,7 +1801,7 @@ int kw_debug_plan(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
   D->dev_b = std::move(P);
   kb->dev = std::move(D);
   PassPlan plan;
-  int rc = plan_pass(env, kb, policies, npol, nullptr, origin, &plan);
+  int rc = plan_pass(env, kb, policies, npol, nullptr, origin, Knobs::on<KW_BULK_DEBUG>(), &plan);
   const TileArgs& T = plan.geom;
   const uint32_t vals[8] = {T.lds_bytes, (uint32_t)plan.launches.size(), (uint32_t)plan.chunks.size(), T.lds_tables,
                             T.rows, T.cmax, T.kmax, T.lmax};

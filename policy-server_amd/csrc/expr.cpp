@@ -2,15 +2,18 @@
 // interpreter (validation, response messages, truth tables), constant folding of call-free
 // subtrees, and the device forms: short-circuit jump code, a truth table, or script bytecode
 // (kwdev.hpp SOp) for the typed stack machine of slots.hpp.
+#define KW_PLANNING_TU  // (knobs.hpp: PlanKnobs only)
 #include "expr.hpp"
 
 #include <cctype>
 #include <climits>
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <set>
 
+#include "knobs.hpp"
 #include "kwdev.hpp"
 #include "unicode_data.hpp"
 
@@ -3138,7 +3141,7 @@ GroupProgram compile_group_expression(const std::string& expr, const std::vector
   }
   // KW_GROUP_FORM=script: every group with member calls takes the bytecode form (a test knob: the
   // CPU suite runs the stack machine through the host walk, the GPU suite through the combine kernel)
-  const bool force_script = getenv("KW_GROUP_FORM") && std::string(getenv("KW_GROUP_FORM")) == "script";
+  const bool force_script = !strcmp(PlanKnobs::str<KW_GROUP_FORM>(), "script");
   const Node* br = bool_root(*ast);
   if (!force_script && ast->fns.empty() && is_bool_subset(br)) {
     uint32_t maxd = 1;

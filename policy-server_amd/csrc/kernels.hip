@@ -25,7 +25,7 @@
 #include "imgscan.hpp"
 #include "kernels.hpp"
 
-// The measured-and-dropped variants of r01-r04 (A/B knobs) are gone from the source; git history
+// The measured-and-dropped variants of r01-r06 (A/B knobs) are gone from the source; git history
 // and DESIGN.md §10 keep what each measured. KW_PREFETCH (kernels.hpp) stays: the next-tile L2
 // prefetch is a documented diagnostic (KW_L2_PREFETCH=1 runs it).
 
@@ -493,20 +493,6 @@ __device__ inline void wglds_x4(const u32x4* src, u32x4* dst, uint32_t n, uint32
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i),
                                      (__attribute__((address_space(3))) void*)(dst + (i - lane)), 16, 0, 0);
 }
-#ifndef KW_DESC_EARLY
-#define KW_DESC_EARLY 1
-#endif
-#ifndef KW_TABLE_DMA  // the workgroup's table staging by LDS-DMA (below)
-#define KW_TABLE_DMA 1
-#endif
-#ifndef KW_P0_SPREAD  // P0 copy jobs spread over the waves (below)
-#define KW_P0_SPREAD 1
-#endif
-__device__ inline void copy_x4(const uint8_t* src, uint8_t* dst, uint32_t bytes, uint32_t tid) {
-  const auto* s = gp((const u32x4*)src);
-  u32x4* d = (u32x4*)dst;
-  for (uint32_t i = tid; i < bytes / 16; i += kSlotThreads) d[i] = s[i];
-}
 
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS (and scalar) operations,
 // not for its outstanding global stores — the verdict stores of a tile drain under the next tile
@@ -578,7 +564,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   };
 
   const uint32_t npol = a.npol;
-  // Tile schedule (capi.cpp sched_dynamic picks one per launch). Workgroup b runs on XCD b % 8 and
+  // Tile schedule (plan.cpp sched_dynamic picks one per launch). Workgroup b runs on XCD b % 8 and
   // serves that XCD's contiguous range of tiles. Static: the range strided by the XCD's
   // workgroups. Dynamic (a.sched): the tiles one at a time from the XCD's own
   // counter (a 128-B line each, so no counter is shared between XCDs); the atomic for the next tile
@@ -624,26 +610,20 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   const uint64_t dbase = t_lo + 2ull * wpx;
   uint64_t tile = t_lo + blockIdx.x / nx, next = tile + wpx;
   // the first tile's descriptor goes out with the table staging below (r06: one memory round trip
-  // fewer before the first tile, which a small shard's ~2 tiles a workgroup feel; KW_DESC_EARLY=0
-  // restores the separate fetch and barrier for A/B)
+  // fewer before the first tile, which a small shard's ~2 tiles a workgroup feel; the A/B against
+  // the separate fetch and barrier: profiles/r06_desc_early_ab.txt)
   // (LDS-table instantiations only: the global-table one, C6, stages no tables and runs 1.2 % slower
   // with the early fetch, profiles/r06_c6_desc_early_ab.txt)
-  constexpr bool desc_early = KW_DESC_EARLY && LDST;
+  constexpr bool desc_early = LDST;
   if (desc_early && tile < t_hi) fetch_desc(tile, 0);
   // ---- once per workgroup: the column classifiers and the chunks' staged record prefixes
   if (LDST) {
-#if KW_TABLE_DMA
     // LDS-DMA: every 16-B piece of the tables in flight at once, one memory latency before the barrier
     // (a copy through VGPRs waits a latency per loop trip: ~3 trips of 256 x 16 B for C4's 12 KB)
     for (uint32_t s = 0; s < t.nstage; ++s)
       glds_x4((const u32x4*)(a.blob + t.stage_blob[s]), (u32x4*)(lds + t.stage_lds[s]), t.stage_bytes[s] / 16u, tid);
     for (uint32_t c = 0; c < t.nchunk; ++c)
       glds_x4((const u32x4*)t.chunk[c].rec, (u32x4*)(lds + t.chunk[c].o_lds), ((const SlotHdr*)t.chunk[c].rec)->staged / 16u, tid);
-#else
-    for (uint32_t s = 0; s < t.nstage; ++s) copy_x4(a.blob + t.stage_blob[s], lds + t.stage_lds[s], t.stage_bytes[s], tid);
-    for (uint32_t c = 0; c < t.nchunk; ++c)
-      copy_x4(t.chunk[c].rec, lds + t.chunk[c].o_lds, ((const SlotHdr*)t.chunk[c].rec)->staged, tid);
-#endif
   }
   __syncthreads();
   mark(7);
@@ -748,7 +728,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
     // and the copies take a few more trips of a cheap loop. r06 (profiles/r06_p0_spread_ab.txt):
     // C4 -3.2 %, C6 -0.7 %; the image-only ones (C2 / C3: one string column) +0.5-1 %, so they
     // keep the workgroup-wide copies.
-    constexpr bool p0_spread = KW_P0_SPREAD && (LBL || CTR);
+    constexpr bool p0_spread = (LBL || CTR);
     if constexpr (p0_spread) {
       auto job = [&](uint32_t j) { return wave == (j & 3u); };
       if (job(0)) wglds_dwords((const uint32_t*)(a.req_flags + r0), (uint32_t*)l_rf, (nr + 3u) >> 2, lane);

@@ -88,7 +88,7 @@ constexpr uint32_t kFeatNfa = 16;
 // wave OR-scan. Its own instantiation, so the others (C4's) keep their code and registers.
 constexpr uint32_t kFeatRng = 32;
 #ifndef KW_PREFETCH  // tile kernel: the code of the next-tile L2 prefetch (run only when the plan asks:
-#define KW_PREFETCH 1   // capi.cpp l2_prefetch, off by default; r02 s60: running it cost C4 0.3442 vs 0.3294 ms)
+#define KW_PREFETCH 1   // plan.cpp l2_prefetch, off by default; r02 s60: running it cost C4 0.3442 vs 0.3294 ms)
 #endif
 #ifndef KW_PF_LANES  // lanes per wave issuing the next tile's L2 prefetch (its LDS landing line: 4 B each)
 #define KW_PF_LANES 64

@@ -1,10 +1,13 @@
 // slotplan.cpp — compile a selected policy list into slot-plan records (slotplan.hpp, slots.hpp).
+#define KW_PLANNING_TU  // (knobs.hpp: PlanKnobs only)
 #include "slotplan.hpp"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+
+#include "knobs.hpp"
 
 namespace kw {
 
@@ -225,8 +228,7 @@ struct Builder {
         rec.push_back(0xff);
       }
       align();
-      static const bool no_mpack = getenv("KW_NO_MPACK") != nullptr;  // A/B knob (kernels built without KW_MAND_BATCH)
-      if (!no_mpack) {
+      if (!PlanKnobs::on<KW_NO_MPACK>()) {  // A/B knob (kernels built without KW_MAND_BATCH)
         h.o_mpack = (uint32_t)rec.size();  // the first 8 keys of each list, packed (the kernel's fast path)
         rec.resize(rec.size() + 8u * std::max<uint32_t>(nslots, 1), 0xff);
         for (uint32_t s = 0; s < nslots; ++s)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Where the instructions go: per KW_TILE_DEBUG ablation bit (capi.cpp), the product kernel's time and
+# Where the instructions go: per KW_TILE_DEBUG ablation bit (knobs.hpp, plan.cpp), the product kernel's time and
 # its VALU / SALU / LDS instruction counts (one rocprofv3 --pmc pass each, kernel-trace only).
 #   CFG=c4_64 DEBUGS="0 1 2 4" bash scripts/ablate_pmc.sh <tag>
 set -u

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Diagnostics of the tile kernel on one box: phase clocks (KW_TILE_DEBUG 512), then the kernel time
-# with phases / sub-phases ablated (KW_TILE_DEBUG bits, capi.cpp), all at C4 unless CFG is set.
+# with phases / sub-phases ablated (KW_TILE_DEBUG bits, knobs.hpp / plan.cpp), all at C4 unless CFG is set.
 set -u
 cd "$(dirname "$0")/.."; OUT=${OUT:-$PWD/bench_out}; mkdir -p "$OUT"
 TAG=${1:-diag}

@@ -20,7 +20,7 @@ NS = "kubewarden"
 @pytest.fixture(autouse=True)
 def _poisoned_verdicts(monkeypatch):
     """Every pass in this module starts from verdict words filled with a sentinel no verdict word
-    equals (KW_POISON_VERDICTS, capi.cpp run_pass): a tile the schedule skipped cannot pass by
+    equals (KW_POISON_VERDICTS, capi.cpp prepare_pass): a tile the schedule skipped cannot pass by
     keeping an earlier pass's words (the failure signature of r02's s45 build)."""
     monkeypatch.setenv("KW_POISON_VERDICTS", "1")
 
@@ -459,3 +459,26 @@ def test_wide_groups_match_oracle():
     full = b.verdicts().reshape(n, len(ids))
     b.validate_rows(env, [int(x) for x in pick], K.VALIDATE)
     assert np.array_equal(b.verdicts(n), full[np.arange(n), pick])
+
+
+def test_plan_cache_follows_planning_knobs(monkeypatch, capfd):
+    """The batch's plan cache is keyed by the KW_* settings planning reads (knobs.cpp kw_knob_hash):
+    a second pass through the same batch with KW_GLOBAL_TABLES switched on plans again (its plan
+    line says lds_tables=0; a stale cached plan would print nothing) and both passes equal the oracle."""
+    monkeypatch.setenv("KW_TILE_DEBUG", "256")
+    monkeypatch.delenv("KW_GLOBAL_TABLES", raising=False)
+    env, oe = _envs("parity")
+    ids = env.policy_ids()
+    syn = K.SynthBatch(0, 512, seed=1)
+    ora = oe.eval(syn.soa(), ids)
+    b = syn.batch().to_device(0)
+    capfd.readouterr()
+    for tables, want in ((None, "lds_tables=1"), ("1", "lds_tables=0")):
+        if tables is not None:
+            monkeypatch.setenv("KW_GLOBAL_TABLES", tables)
+        b.validate(env, ids)
+        gpu = b.verdicts()
+        err = capfd.readouterr().err
+        assert np.array_equal(gpu, ora), diff_verdicts(gpu, ora, len(ids), ids)
+        plan_lines = [ln for ln in err.splitlines() if ln.startswith("[kw tile] lds_tables=")]
+        assert plan_lines and all(want in ln for ln in plan_lines), (tables, err)
