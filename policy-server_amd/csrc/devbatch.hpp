@@ -1,5 +1,5 @@
 // devbatch.hpp — the handles behind include/kwgpu.h (kw_env, kw_batch), the device copy of a batch
-// (DeviceBatch) and the plan of one pass over it (PassPlan; plan.cpp fills it, capi.cpp runs it).
+// (DeviceBatch) and the plan of one pass over it (PassPlan; plan.cpp fills it, pass.cpp runs it).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -128,7 +128,7 @@ struct DeviceBatch {
   std::vector<uint64_t> perm;
   uint64_t split = 0;
   std::unique_ptr<Batch> dev_b;
-  // the last all-pairs pass's plan (capi.cpp validate_cached): reused while the
+  // the last all-pairs pass's plan (pass.cpp validate_cached): reused while the
   // environment, the policy list, the origin and every KW_* setting stay the same — planning a
   // 64-policy pass is ~60-300 us of host time, the whole GPU time of a small shard
   std::shared_ptr<PassPlan> plan_cache;

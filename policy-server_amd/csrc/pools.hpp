@@ -9,6 +9,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 namespace kw {
@@ -199,6 +200,59 @@ struct CopySeg {
 BlockPool& dev_pool();
 BlockPool& host_pool();
 StreamPool& stream_pool();
+
+// Move-only owners of what a call takes from the pools: it goes back when the owner dies.
+// The owner's user drains the streams that touch a block or an event before that (bulk.cpp Res).
+struct BlockLease {
+  BlockPool* pool = nullptr;
+  int dev = -1;
+  void* p = nullptr;
+  size_t bytes = 0;
+  BlockLease() = default;
+  BlockLease(BlockLease&& o) noexcept : pool(o.pool), dev(o.dev), p(o.p), bytes(o.bytes) { o.p = nullptr; }
+  ~BlockLease() { reset(); }
+  // a block of n bytes of P in place of the one held
+  hipError_t alloc(BlockPool& P, int d, size_t n) {
+    reset();
+    pool = &P, dev = d, bytes = n;
+    return P.alloc(d, n, &p);
+  }
+  void reset() {
+    if (p) pool->release(dev, p, bytes);
+    p = nullptr;
+  }
+};
+
+struct StreamLease {
+  int dev = -1;
+  hipStream_t s = nullptr;
+  StreamLease() = default;
+  StreamLease(StreamLease&& o) noexcept : dev(o.dev), s(o.s) { o.s = nullptr; }
+  ~StreamLease() { stream_pool().put(dev, s); }
+  hipError_t get(int d) {
+    dev = d;
+    return stream_pool().get(d, &s);
+  }
+};
+
+struct EventLease {
+  int dev = -1;
+  std::vector<hipEvent_t> ev;
+  EventLease() = default;
+  EventLease(EventLease&& o) noexcept : dev(o.dev), ev(std::move(o.ev)) { o.ev.clear(); }
+  ~EventLease() {
+    for (hipEvent_t e : ev) stream_pool().put(dev, e);
+  }
+  // n events; on an error the ones already taken stay owned
+  hipError_t get(int d, size_t n) {
+    dev = d;
+    ev.assign(n, nullptr);
+    for (hipEvent_t& e : ev)
+      if (hipError_t rc = stream_pool().get(d, &e)) return rc;
+    return hipSuccess;
+  }
+  hipEvent_t operator[](size_t i) const { return ev[i]; }
+};
 
 // Host copy spread over up to 16 threads for large buffers (staging fills and verdict read-back:
 // one thread moves ≈ 10 GB/s, the host's memory system several times that).

@@ -1,4 +1,4 @@
-"""Same-process A/B of the light / heavy split (capi.cpp split_rows) on C5 at 10M requests: the
+"""Same-process A/B of the light / heavy split (upload.cpp split_rows) on C5 at 10M requests: the
 unsplit upload against split uploads under heavy thresholds (KW_HEAVY_CTR, at upload) and
 heavy-region tile heights (KW_HEAVY_ROWS, at planning), each timed with HIP events around the pass
 (kw_validate_timed), interleaved over rounds.

@@ -52,10 +52,11 @@ def test_bulk_matches_oracle(name, scfg, rows, chunk):
 
 
 def test_bulk_more_than_256_chunks_pageable_output():
-    """past 256 chunks the last chunk takes every remaining tile, so it is
-    larger than one full chunk. The pageable output's bounce blocks must be sized for it.
-    64-row C4 tiles, chunk_rows=128 (two tiles a chunk after the ramp) on 100k rows: the last of
-    the 256 chunks holds about 1,100 tiles."""
+    """a chunk_rows that would give more than about 240 chunks makes every chunk
+    grow instead (bulkplan.hpp chunk_tiles), so a chunk is larger than chunk_rows asks. The
+    pageable output's bounce blocks must be sized for the largest chunk, not for chunk_rows.
+    64-row C4 tiles, chunk_rows=128 (two tiles) on 100k rows (1,563 tiles): full chunks of 7 tiles,
+    448 rows, after the ramp."""
     env, oe = _envs(config("c4_64"))
     ids = env.policy_ids()
     syn = K.SynthBatch(4, 100000, seed=4257)

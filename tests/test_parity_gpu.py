@@ -20,7 +20,7 @@ NS = "kubewarden"
 @pytest.fixture(autouse=True)
 def _poisoned_verdicts(monkeypatch):
     """Every pass in this module starts from verdict words filled with a sentinel no verdict word
-    equals (KW_POISON_VERDICTS, capi.cpp prepare_pass): a tile the schedule skipped cannot pass by
+    equals (KW_POISON_VERDICTS, pass.cpp prepare_pass): a tile the schedule skipped cannot pass by
     keeping an earlier pass's words (the failure signature of r02's s45 build)."""
     monkeypatch.setenv("KW_POISON_VERDICTS", "1")
 

@@ -3,7 +3,7 @@ tests/golden/plan_words.json: all 16 words, for every configuration at 5,000 and
 (c2_trusted also at 600,000, the taller-tile branch), under each setting of the live planning knobs.
 A plan that fails records its return code.
 
-The file holds what the library planned before plan_pass moved out of capi.cpp. The test only
+The file holds what the library planned before plan_pass became a file of its own (plan.cpp). The test only
 reads it. `PYTHONPATH=policy-server_amd:tests python tests/test_plan_golden.py` rewrites it from the
 library KWGPU_LIB names, which must be a build of a commit whose plans are known good (never the
 code under test).

@@ -1,4 +1,4 @@
-"""Light / heavy split at upload (capi.cpp split_rows / permute_batch):
+"""Light / heavy split at upload (upload.cpp split_rows / permute_batch):
 a batch whose heavy requests (more than 5 containers) are 1-50 % of the rows and hold >= 30 % of
 the containers goes to the device with its light rows first and its heavy rows after them, each
 region with its own tile geometry; verdict words and side data are scattered back to batch rows at
