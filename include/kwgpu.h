@@ -261,6 +261,23 @@ int kw_debug_host_walk(const kw_env *env, const kw_batch *b, const int32_t *poli
 int kw_debug_plan(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin, uint32_t *out,
                   int cap);
 
+/* Diagnostic (tests): the staging copy jobs of the tile kernel for an all-pairs pass planned over the
+ * batch's host columns (nothing launched), with every tile descriptor and the span the kernel's own
+ * span function gives each job in it. out (u32 words): regions; then per region
+ *   8 words: requests per tile, jobs, descriptors, overflow requests, first and end row, LDS bytes,
+ *            the light region's rows (0: batch order);
+ *   20 words: LDS offsets of the staged request flags, container / label offsets, container flags,
+ *            added / dropped capability offsets, then of each string column's offsets [7] and bytes [7]
+ *            (0: not staged);
+ *   per job 4 words: column (0-5 the arrays above in that order, 6 + 2m / 7 + 2m string column m's
+ *            offsets / bytes), LDS destination, bytes per piece (4 or 16), the job's code;
+ *   per descriptor 32 descriptor words, then per job 3 words: byte offset into the column (low,
+ *            high) and pieces to copy;
+ *   the overflow requests' rows.
+ * *needed: the words of the whole record; KW_E_NOSPACE when cap is smaller (out untouched). */
+int kw_debug_copy_jobs(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
+                       uint32_t *out, size_t cap, size_t *needed);
+
 /* Diagnostic (tests): the device-row order kw_batch_to_device gives this batch — the light / heavy
  * split (rows with more than 5 containers after the others when they are 1-50 % of
  * a batch of >= 2^18 rows and hold >= 30 % of its containers; KW_SPLIT=0 / 1 never / always) — as a

@@ -570,6 +570,63 @@ int kw_debug_plan(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
   return rc;
 }
 
+int kw_debug_copy_jobs(const kw_env* env, kw_batch* kb, const int32_t* policies, uint32_t npol, int origin, uint32_t* out,
+                       size_t cap, size_t* needed) {
+  if (!env || !kb || !needed || (!out && cap) || (!policies && npol)) return KW_E_ARG;
+  std::unique_ptr<DeviceBatch> saved = std::move(kb->dev);
+  kb->dev = host_view(kb);
+  const DeviceBatch& D = *kb->dev;
+  const Batch& B = dev_rows(kb);
+  PassPlan plan;
+  int rc = plan_pass(env, kb, policies, npol, nullptr, origin, false, &plan);
+  std::vector<uint32_t> w;
+  if (rc == KW_OK) {
+    // a job's column by its base address: 0-5 the request / container arrays, then per staged
+    // string column 6 + 2m its offsets and 7 + 2m its bytes
+    const void* cols[kMaxCopyJobs] = {D.req_flags, D.ctr_off, D.lbl_off, D.ctr_flags, D.capadd_off, D.capdrop_off};
+    for (int m = 0; m < (int)NSTR; ++m) cols[6 + 2 * m] = D.str[m].off, cols[7 + 2 * m] = D.str[m].bytes;
+    w.push_back((uint32_t)plan.regions.size());
+    for (const PassPlan::Region& rg : plan.regions) {
+      const TileArgs& T = rg.geom;
+      std::vector<TileDesc> desc;
+      std::vector<uint32_t> ovf;
+      const uint64_t ntiles = (rg.hi - rg.lo + T.rows - 1) / T.rows;
+      if ((rc = build_descs(B, T, rg.lo, rg.hi, 0, ntiles, 4096, &desc, &ovf))) break;
+      for (uint32_t v : {T.rows, T.njobs, (uint32_t)desc.size(), (uint32_t)ovf.size(), (uint32_t)rg.lo, (uint32_t)rg.hi, T.lds_bytes,
+                         (uint32_t)D.split})
+        w.push_back(v);
+      for (uint32_t v : {T.o_rf, T.o_coff, T.o_loff, T.o_cflags, T.o_cadd, T.o_cdrop}) w.push_back(v);
+      w.insert(w.end(), T.o_so, T.o_so + NSTR);
+      w.insert(w.end(), T.o_sb, T.o_sb + NSTR);
+      for (uint32_t j = 0; j < T.njobs; ++j) {
+        const CopyJob& q = T.jobs[j];
+        uint32_t col = 0xffffffffu;
+        // (an unstaged column may share the host view's placeholder address: staged columns only)
+        for (uint32_t c = 0; c < kMaxCopyJobs; ++c)
+          if ((c < 6 || T.o_sb[(c - 6) / 2]) && q.base == (uint64_t)(uintptr_t)cols[c] && col == 0xffffffffu) col = c;
+        for (uint32_t v : {col, copy_lds(q.code), (q.code & kCjX4) ? 16u : 4u, q.code}) w.push_back(v);
+      }
+      for (const TileDesc& d : desc) {
+        const uint32_t* dw = (const uint32_t*)&d;
+        w.insert(w.end(), dw, dw + sizeof(TileDesc) / 4);
+        for (uint32_t j = 0; j < T.njobs; ++j) {
+          const uint32_t code = T.jobs[j].code;
+          const CopySpan sp = copy_span(code, dw[code & 31u], dw[(code >> 5) & 31u], d.r0hi);
+          for (uint32_t v : {(uint32_t)sp.byte_off, (uint32_t)(sp.byte_off >> 32), sp.count}) w.push_back(v);
+        }
+      }
+      w.insert(w.end(), ovf.begin(), ovf.end());
+    }
+  }
+  kb->dev->verdicts = nullptr;  // host memory: not the DeviceBatch's to free
+  kb->dev = std::move(saved);
+  if (rc) return rc;
+  *needed = w.size();
+  if (cap < w.size()) return KW_E_NOSPACE;
+  std::copy(w.begin(), w.end(), out);
+  return KW_OK;
+}
+
 int kw_debug_reorder(const kw_batch* kb, uint64_t* perm, size_t cap, uint64_t* split, kw_batch** out) {
   if (!kb || !split || !out || (!perm && kb->b.n) || cap < kb->b.n) return KW_E_ARG;
   std::vector<uint64_t> p;

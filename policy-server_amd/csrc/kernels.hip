@@ -470,12 +470,6 @@ __device__ inline uint32_t str_n(int m, uint32_t nr, uint32_t nc, uint32_t nka, 
 // LDS-DMA copies (global_load_lds) issued by every wave of the workgroup: the LDS image is
 // wave-linear (wave-uniform base + lane x size), so lane l of the wave whose first element is i - l
 // lands at dst + i. Tails are masked by the loop bound.
-__device__ inline void glds_dwords(const uint32_t* src, uint32_t* dst, uint32_t n, uint32_t tid) {
-  const uint32_t lane = tid & 63u;
-  for (uint32_t i = tid; i < n; i += kSlotThreads)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i),
-                                     (__attribute__((address_space(3))) void*)(dst + (i - lane)), 4, 0, 0);
-}
 __device__ inline void glds_x4(const u32x4* src, u32x4* dst, uint32_t n, uint32_t tid) {
   const uint32_t lane = tid & 63u;
   for (uint32_t i = tid; i < n; i += kSlotThreads)
@@ -686,6 +680,17 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   const ImgLayout il = t.il;
   const uint32_t nim = il.n(), nlv = t.nlv;
   const uint32_t need = t.need;
+  // P0's copy jobs (TileArgs::jobs, built by the planner): lane j of every wave holds job j for the
+  // whole kernel — its column address and the code that gives its LDS destination and a tile's
+  // span from the tile's descriptor (copy_span).
+  const uint32_t njobs = t.njobs;
+  uint32_t jb_lo = 0, jb_hi = 0, jb_code = 0;
+  if (lane < njobs) {
+    const CopyJob q = tp->jobs[lane];
+    jb_lo = (uint32_t)q.base;
+    jb_hi = (uint32_t)(q.base >> 32);
+    jb_code = q.code;
+  }
 
   if (!desc_early) {
     if (tile < t_hi) fetch_desc(tile, 0);
@@ -707,11 +712,6 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
       next = dyn ? dbase + l_nx[cur] : next + wpx;
       continue;
     }
-    const uint64_t r0 = ((uint64_t)KW_DF(d.r0hi) << 32) | KW_DF(d.r0lo);
-    const uint32_t nr = KW_DF(d.nr);
-    const uint32_t cb = KW_DF(d.cb), ce = KW_DF(d.ce), lb = KW_DF(d.lb), le = KW_DF(d.le);
-    const uint32_t kab = KW_DF(d.kab), kae = KW_DF(d.kae), kdb = KW_DF(d.kdb), kde = KW_DF(d.kde);
-    const uint32_t nc = ce - cb, nl = le - lb;
     uint64_t p0_t1 = 0, p0_t2 = 0;
     if (timing) {
       p0_t1 = clock64();
@@ -721,59 +721,47 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
     // ---- P0: stage request headers, container offsets and the tile's strings. Every copy is an
     //      LDS-DMA (global_load_lds: no VGPR round trip), so all of a tile's loads are in flight
     //      together and the barrier waits for one memory latency, not one per array.
-    // Label / container instantiations (several staged string columns): each copy job runs on one
-    // wave (job j on wave j % 4). A job's setup is a chain of dependent round trips (the column's
-    // addresses are scalar loads from TileArgs, its span descriptor fields LDS reads, each waited
-    // for before the copy can issue); spread over the waves, each wave waits for a quarter of them,
-    // and the copies take a few more trips of a cheap loop. r06 (profiles/r06_p0_spread_ab.txt):
-    // C4 -3.2 %, C6 -0.7 %; the image-only ones (C2 / C3: one string column) +0.5-1 %, so they
-    // keep the workgroup-wide copies.
-    constexpr bool p0_spread = (LBL || CTR);
-    if constexpr (p0_spread) {
-      auto job = [&](uint32_t j) { return wave == (j & 3u); };
-      if (job(0)) wglds_dwords((const uint32_t*)(a.req_flags + r0), (uint32_t*)l_rf, (nr + 3u) >> 2, lane);
-      if (job(1)) wglds_dwords(a.ctr_off + r0, l_coff, nr + 1, lane);
-      if (job(2)) wglds_dwords(a.lbl_off + r0, l_loff, nr + 1, lane);
-      if (job(3)) wglds_dwords((const uint32_t*)a.ctr_flags + (cb >> 2), (uint32_t*)l_cflags, ((ce + 3u) >> 2) - (cb >> 2), lane);
-      if (job(4)) wglds_dwords(a.capadd_off + cb, l_cadd, nc + 1, lane);
-      if (job(5)) wglds_dwords(a.capdrop_off + cb, l_cdrop, nc + 1, lane);
+    // Nothing here depends on the tile's contents, only on its descriptor, so the planner has
+    // reduced every array to a copy job (kernels.hpp CopyJob) and lane j holds job j. Per tile, lane
+    // j reads its job's two descriptor words from LDS and computes the job's source address and
+    // piece count (copy_span: one LDS round trip and one run of VALU arithmetic for all jobs, where
+    // r06 walked ~5 dependent scalar chains per wave: column pointers and LDS offsets scalar-loaded
+    // from TileArgs, span fields read from LDS one by one). Each wave then takes its jobs (j = wave,
+    // wave + 4, ...: the planner orders them so the waves' copy instructions balance), four
+    // v_readlane each, and issues the dword or 16-byte copy loop. The descriptor's scalar fields,
+    // which only P1-P3 use, are read after the copies are issued, under their flight.
+    // profiles/r07_p0_jobs_ab.txt: C4 -3.3 %, C5 -3.4 %, C6 -1.6 %, C1 -5.6 %, C2 -9.3 %, C3 -1 %.
+    {
+      const uint32_t* dw = (const uint32_t*)&d;
+      // (the code is decoded here, per tile: hoisted out of the tile loop, its ten decoded fields
+      // would each hold a register for the whole kernel)
+      uint32_t code_v = jb_code;
+      asm volatile("" : "+v"(code_v));
+      const CopySpan sp = copy_span(code_v, dw[code_v & 31u], dw[(code_v >> 5) & 31u], d.r0hi);
+      const uint64_t src = (((uint64_t)jb_hi << 32) | jb_lo) + sp.byte_off;
+      const uint32_t s_lo = (uint32_t)src, s_hi = (uint32_t)(src >> 32);
       if (timing) {
         p0_t2 = clock64();
         sg_add(SG_P0_REQ, p0_t2 - p0_t1);
       }
-#pragma unroll
-      for (int m = 0; m < (int)NSTR; ++m) {
-        const uint32_t jo = 6u + 2u * (uint32_t)m, jb = jo + 1u;
-        if (!(job(jo) || job(jb)) || !t.o_sb[m]) continue;
-        if (job(jo)) {
-          const uint32_t g0 = str_g0(m, (uint32_t)r0, cb, kab, kdb, lb);
-          const uint32_t n = str_n(m, nr, nc, kae - kab, kde - kdb, nl);
-          wglds_dwords(t.s_off[m] + g0, (uint32_t*)(lds + t.o_so[m]), n + 1, lane);  // absolute: rebased by l_sa
-        } else {
-          wglds_x4((const u32x4*)(t.s_bytes[m] + KW_DF(d.sa[m])), (u32x4*)(lds + t.o_sb[m]), KW_DF(d.nv[m]), lane);
-        }
-      }
-    } else {
-      glds_dwords((const uint32_t*)(a.req_flags + r0), (uint32_t*)l_rf, (nr + 3u) >> 2, tid);
-      glds_dwords(a.ctr_off + r0, l_coff, nr + 1, tid);
-      glds_dwords(a.lbl_off + r0, l_loff, nr + 1, tid);
-      glds_dwords((const uint32_t*)a.ctr_flags + (cb >> 2), (uint32_t*)l_cflags, ((ce + 3u) >> 2) - (cb >> 2), tid);
-      glds_dwords(a.capadd_off + cb, l_cadd, nc + 1, tid);
-      glds_dwords(a.capdrop_off + cb, l_cdrop, nc + 1, tid);
-      if (timing) {
-        p0_t2 = clock64();
-        sg_add(SG_P0_REQ, p0_t2 - p0_t1);
-      }
-#pragma unroll
-      for (int m = 0; m < (int)NSTR; ++m) {
-        if (!t.o_sb[m]) continue;
-        const uint32_t g0 = str_g0(m, (uint32_t)r0, cb, kab, kdb, lb);
-        const uint32_t n = str_n(m, nr, nc, kae - kab, kde - kdb, nl);
-        glds_dwords(t.s_off[m] + g0, (uint32_t*)(lds + t.o_so[m]), n + 1, tid);  // absolute: rebased by l_sa
-        glds_x4((const u32x4*)(t.s_bytes[m] + KW_DF(d.sa[m])), (u32x4*)(lds + t.o_sb[m]), KW_DF(d.nv[m]), tid);
+      for (uint32_t j = wave; j < njobs; j += kSlotThreads / 64u) {
+        const uint64_t p = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)s_hi, (int)j) << 32) |
+                           (uint32_t)__builtin_amdgcn_readlane((int)s_lo, (int)j);
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)sp.count, (int)j);
+        const uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)code_v, (int)j);
+        uint8_t* dst = lds + copy_lds(code);
+        if (code & kCjX4)
+          wglds_x4((const u32x4*)p, (u32x4*)dst, n, lane);
+        else
+          wglds_dwords((const uint32_t*)p, (uint32_t*)dst, n, lane);  // (string offsets stay absolute: rebased by l_sa)
       }
     }
+    const uint64_t r0 = ((uint64_t)KW_DF(d.r0hi) << 32) | KW_DF(d.r0lo);
+    const uint32_t nr = KW_DF(d.nr);
+    const uint32_t cb = KW_DF(d.cb), ce = KW_DF(d.ce), lb = KW_DF(d.lb), le = KW_DF(d.le);
+    const uint32_t kab = KW_DF(d.kab), kae = KW_DF(d.kae), kdb = KW_DF(d.kdb), kde = KW_DF(d.kde);
     if (timing) sg_add(SG_P0_STR, clock64() - p0_t2);
+    const uint32_t nc = ce - cb, nl = le - lb;
     for (uint32_t i = tid; i < nr; i += kSlotThreads) l_rej[i] = l_mut[i] = 0;
     if (DYNB && tid == 0) l_nx[2] = l_nx[3] = 0;  // P1 / P2 block counters (below)
     if (tid < NSTR) l_sa[tid] = d.sa[tid];

@@ -56,7 +56,9 @@ enum Seg : uint32_t {
   SG_P1_LABEL = 0, SG_P1_CAPSTR, SG_P1_CTR, SG_P1_IMAGE, SG_P1_REQ, SG_P2_CTR, SG_P2_LABEL, SG_P2_REQ,
   SG_P1_BUSY, SG_P1_WAIT, SG_P2_BUSY, SG_P2_WAIT, SG_P0_WAIT, SG_P3_BUSY, SG_P3_WAIT,
   SG_START,  // the workgroup's start (s_memrealtime, 100 MHz): residency of the grid
-  SG_P0_TOP, SG_P0_REQ, SG_P0_STR,  // P0 issue: tile loop top to the descriptor fields, request-array copies, string copies
+  // P0 issue: tile loop top to the descriptor's `fits`; the jobs' spans (copy_span on every lane); the
+  // wave's job loop (readlanes and copies)
+  SG_P0_TOP, SG_P0_REQ, SG_P0_STR,
   kSegWords = 19
 };
 constexpr uint32_t kPhaseWords = 8 + kSegWords;
@@ -103,6 +105,45 @@ struct ChunkArgs {
   uint64_t init;
 };
 
+// One array a tile stages (P0 of the tile kernel): the column's device address, where it lands in
+// LDS, and how the tile's span of it follows from two words of the tile's descriptor (TileDesc as
+// u32 words). The planner fills one table per launch (plan.cpp build_copy_jobs); in the kernel lane j
+// holds job j (three registers), so every job's span is one round of the same arithmetic
+// (copy_span) on all lanes.
+// code: bits 0-4 / 5-9 the descriptor words B and E; kCjRel: E counts from B (else E is the end);
+// kCjReq: B is a request index, its high half in TileDesc::r0hi; kCjQuad: the span is counted in
+// pieces of 4 elements, rounded up (byte arrays copied as dwords); kCjAlign: B is first aligned down
+// to a piece; kCjPlus1: one piece more (an offsets array has n + 1 entries); kCjElem4: 4-byte
+// elements, else bytes; kCjX4: 16-byte pieces, else dwords; bits 18-31: the LDS destination / 16.
+struct CopyJob {
+  uint64_t base;
+  uint32_t code;
+  uint32_t pad;
+};
+constexpr uint32_t kCjRel = 1u << 10, kCjReq = 1u << 11, kCjQuad = 1u << 12, kCjAlign = 1u << 13, kCjPlus1 = 1u << 14,
+                   kCjElem4 = 1u << 15, kCjX4 = 1u << 16, kCjLdsShift = 18;
+constexpr uint32_t copy_code(uint32_t wb, uint32_t we, uint32_t lds, uint32_t flags) {
+  return wb | (we << 5) | flags | ((lds >> 4) << kCjLdsShift);
+}
+KW_HD constexpr uint32_t copy_lds(uint32_t code) { return (code >> kCjLdsShift) << 4; }
+struct CopySpan {
+  uint64_t byte_off;  // from CopyJob::base
+  uint32_t count;     // pieces (dwords, or 16-byte vectors with kCjX4)
+};
+// The span of a job in a tile: b = desc[code & 31], e = desc[(code >> 5) & 31], r0hi = TileDesc::r0hi.
+// Selections are masks and shifts, not branches: the lanes of a wave hold jobs of every kind.
+KW_HD inline CopySpan copy_span(uint32_t code, uint32_t b, uint32_t e, uint32_t r0hi) {
+  const uint32_t sh = (code >> 11) & 2u, bsh = (code >> 14) & 2u, rnd = (1u << sh) - 1u;  // kCjQuad, kCjElem4: 0 or 2
+  const uint32_t rel = 0u - ((code >> 10) & 1u), req = 0u - ((code >> 11) & 1u), al = 0u - ((code >> 13) & 1u);
+  const uint32_t b0 = b & ~(rnd & al);
+  const uint32_t end = e + (b & rel);
+  CopySpan s;
+  s.count = ((end - b0 + rnd) >> sh) + ((code >> 14) & 1u);
+  s.byte_off = (((uint64_t)(r0hi & req) << 32) | b0) << bsh;
+  return s;
+}
+constexpr uint32_t kMaxCopyJobs = 6 + 2 * NSTR;
+
 // Per-launch geometry and LDS layout. Lives in device memory; the kernel reads it with scalar loads.
 struct TileArgs {
   uint32_t rows;                  // requests per tile
@@ -130,6 +171,10 @@ struct TileArgs {
   uint32_t o_so[NSTR], o_sb[NSTR], sb_cap[NSTR];  // staged string offsets / bytes (0 = not staged)
   const uint32_t* s_off[NSTR];
   const uint8_t* s_bytes[NSTR];
+  // P0's copy jobs: the six request / container arrays, then offsets and bytes of each staged string
+  // column, ordered so that job j on wave j % 4 balances the waves' copy instructions
+  CopyJob jobs[kMaxCopyJobs];
+  uint32_t njobs;
   // column classifiers: LDS offsets when staged (lds_tables), blob offsets always
   uint32_t lds_tables;
   uint32_t lit_lds[NCOL], dfa_lds[NCOL], kv_lds;
@@ -162,6 +207,10 @@ struct alignas(16) TileDesc {
   uint32_t pad[4];
 };
 static_assert(sizeof(TileDesc) == 128, "TileDesc layout");
+
+// Fills T->jobs / njobs (plan.cpp) from T's LDS layout and string columns and the batch's six
+// request / container arrays cols[] = {req_flags, ctr_off, lbl_off, ctr_flags, capadd_off, capdrop_off}.
+void build_copy_jobs(TileArgs* T, const void* const cols[6]);
 
 // One launch of the tile kernel over chunks t.chunk[0..nchunk). t: host copy (launch geometry);
 // d_t: the same TileArgs resident in device memory (read by the kernel).

@@ -664,6 +664,8 @@ void share_fields(TileArgs& T, const DevHeader* H, const PassNeeds& N, const Tab
     T.kv_lds = 0;
   }
   T.debug = debug;  // phase ablation (diagnostics)
+  const void* const cols[6] = {D.req_flags, D.ctr_off, D.lbl_off, D.ctr_flags, D.capadd_off, D.capdrop_off};
+  build_copy_jobs(&T, cols);
 }
 
 // KW_TILE_DEBUG & 256: a region's plan on stderr (scripts/diag.sh reads these lines).
@@ -748,6 +750,52 @@ int plan_eval_args(const Env& E, const Batch& B, const DeviceBatch& D, const Pas
 }
 
 }  // namespace
+
+// ---- P0's copy-job table (kernels.hpp CopyJob) from a TileArgs whose LDS layout and string
+// columns are set. Descriptor words by their position in TileDesc.
+void build_copy_jobs(TileArgs* Tp, const void* const cols[6]) {
+  TileArgs& T = *Tp;
+  constexpr uint32_t W_CB = offsetof(TileDesc, cb) / 4, W_CE = offsetof(TileDesc, ce) / 4, W_LB = offsetof(TileDesc, lb) / 4,
+                     W_LE = offsetof(TileDesc, le) / 4, W_KAB = offsetof(TileDesc, kab) / 4, W_KAE = offsetof(TileDesc, kae) / 4,
+                     W_KDB = offsetof(TileDesc, kdb) / 4, W_KDE = offsetof(TileDesc, kde) / 4, W_SA = offsetof(TileDesc, sa) / 4,
+                     W_NV = offsetof(TileDesc, nv) / 4, W_R0 = offsetof(TileDesc, r0lo) / 4, W_NR = offsetof(TileDesc, nr) / 4;
+  static_assert(W_NR < 32 && offsetof(TileDesc, r0hi) / 4 == W_R0 + 1, "copy_code holds 5-bit descriptor words");
+  struct Todo {
+    CopyJob j;
+    uint32_t trips;  // copy instructions a wave issues for a tile at the layout's capacities
+  };
+  std::vector<Todo> todo;
+  auto add = [&](const void* base, uint32_t code, uint32_t pieces) {
+    todo.push_back({{(uint64_t)(uintptr_t)base, code, 0u}, (pieces + 63u) / 64u});
+  };
+  const uint32_t req = kCjRel | kCjReq, offs = kCjElem4 | kCjPlus1;  // request-indexed; an offsets array
+  add(cols[0], copy_code(W_R0, W_NR, T.o_rf, req | kCjQuad), (T.rows + 3) / 4);
+  add(cols[1], copy_code(W_R0, W_NR, T.o_coff, req | offs), T.rows + 1);
+  add(cols[2], copy_code(W_R0, W_NR, T.o_loff, req | offs), T.rows + 1);
+  add(cols[3], copy_code(W_CB, W_CE, T.o_cflags, kCjQuad | kCjAlign), (T.cmax + 3) / 4 + 1);
+  add(cols[4], copy_code(W_CB, W_CE, T.o_cadd, offs), T.cmax + 1);
+  add(cols[5], copy_code(W_CB, W_CE, T.o_cdrop, offs), T.cmax + 1);
+  for (uint32_t m = 0; m < NSTR; ++m) {
+    if (!T.o_sb[m]) continue;
+    uint32_t wb = W_CB, we = W_CE, fl = offs, cap = T.cmax;
+    if (m == S_NS) wb = W_R0, we = W_NR, fl |= req, cap = T.rows;
+    else if (m == S_CAPADD) wb = W_KAB, we = W_KAE, cap = T.kmax;
+    else if (m == S_CAPDROP) wb = W_KDB, we = W_KDE, cap = T.kmax;
+    else if (m == S_LK || m == S_LV) wb = W_LB, we = W_LE, cap = T.lmax;
+    add(T.s_off[m], copy_code(wb, we, T.o_so[m], fl), cap + 1);
+    add(T.s_bytes[m], copy_code(W_SA + m, W_NV + m, T.o_sb[m], kCjRel | kCjX4), T.sb_cap[m] / 16);
+  }
+  // job j runs on wave j % 4: the longest jobs first, dealt to the waves back and forth, so each
+  // wave's copy instructions come out about even
+  std::stable_sort(todo.begin(), todo.end(), [](const Todo& a, const Todo& b) { return a.trips > b.trips; });
+  memset(T.jobs, 0, sizeof(T.jobs));
+  T.njobs = (uint32_t)todo.size();
+  for (uint32_t k = 0; k < T.njobs; ++k) {
+    const uint32_t row = k / 4u, i = k % 4u;
+    const uint32_t len = std::min(4u, T.njobs - row * 4u);  // (the last row may be short)
+    T.jobs[row * 4u + ((row & 1u) ? len - 1u - i : i)] = todo[k].j;
+  }
+}
 
 // Plan one pass: slot-plan chunks of the policy list, the launches they take, the tile geometry
 // and LDS layout, the kernel arguments.

@@ -416,6 +416,21 @@ class Batch:
                 "grid", "heavy_lds_bytes", "heavy_rows", "heavy_cmax", "heavy_grid", "scan_regions")
         return dict(zip(keys, out[:16]))
 
+    def debug_copy_jobs(self, env, policies, origin=VALIDATE):
+        """Diagnostic (kw_debug_copy_jobs): the record of the tile kernel's staging copy jobs for an
+        all-pairs pass planned on the host, as a uint32 array (layout: include/kwgpu.h)."""
+        import numpy as np
+        arr = env._array(policies)
+        need = C.c_size_t()
+        rc = self._L.kw_debug_copy_jobs(env._h, self._h, arr, len(policies), origin, None, 0, C.byref(need))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_debug_copy_jobs failed")
+        out = np.zeros(max(need.value, 1), dtype=np.uint32)
+        rc = self._L.kw_debug_copy_jobs(env._h, self._h, arr, len(policies), origin,
+                                        out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(need))
+        raise_for(rc, "kw_debug_copy_jobs failed")
+        return out[:need.value]
+
     def debug_reorder(self):
         """Diagnostic (kw_debug_reorder): the device-row order kw_batch_to_device gives this batch,
         as (batch in that order, perm, light-region rows); perm[d] is the batch row at device row d."""
