@@ -278,6 +278,33 @@ int kw_debug_plan(const kw_env *env, kw_batch *b, const int32_t *policies, uint3
 int kw_debug_copy_jobs(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
                        uint32_t *out, size_t cap, size_t *needed);
 
+/* Diagnostic (tests): the tile descriptors a resident all-pairs pass would upload, planned over the
+ * batch's host columns (nothing launched), cut per tile at the least estimated cost per row
+ * (KW_TILE_CUT), in row order. out (u32 words): regions, overflow requests; then per region
+ *   10 words: requests per tile, container / capability / label capacity, grid, XCDs the grid's
+ *            workgroups spread over (nx), schedule (0 strided, 1 dynamic), descriptors, first and end row;
+ *   7 + 7 words: per string column whether it is staged, and its byte capacity;
+ *   per descriptor, in array order, 34 words: the 32 descriptor words (first request at words 24-25,
+ *            requests 26, fits 23; entity ranges 0-7) and the estimated cost in wave-cycles (low, high;
+ *            0 for a descriptor queued for the overflow kernels);
+ * then the overflow requests' rows. Rows are device rows (kw_debug_reorder).
+ * *needed: the words of the whole record; KW_E_NOSPACE when cap is smaller (out untouched). */
+int kw_debug_tile_descs(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
+                        uint32_t *out, size_t cap, size_t *needed);
+
+/* Diagnostic (tests): the planner's estimated cost in wave-cycles of a tile with these item counts,
+ * for a launch of the family set `feat` (bits: 1 image, 2 label, 4 container, 8 group) that classifies
+ * the string columns `need` (bit per column: 0 namespace, 1 image, 2 AppArmor, 3 / 4 added / dropped
+ * capabilities, 5 / 6 label keys / values). */
+uint64_t kw_debug_tile_cost(uint32_t feat, uint32_t need, uint32_t requests, uint32_t labels, uint32_t containers,
+                            uint32_t capabilities);
+
+/* Diagnostic (tests): the tile schedule's index arithmetic as the kernel and the planner share it,
+ * for `workgroup` of a launch of `grid` workgroups over ndesc descriptors. out[0..7): XCDs in use, the
+ * workgroup's XCD, its slot in that XCD, the XCD's workgroups, the XCD's descriptor range [lo, hi),
+ * and the descriptor the slot runs as its `tile`-th tile on the strided schedule (one only while < hi). */
+int kw_debug_tile_slot(uint64_t ndesc, uint32_t grid, uint32_t workgroup, uint32_t tile, uint64_t *out);
+
 /* Diagnostic (tests): the device-row order kw_batch_to_device gives this batch — the light / heavy
  * split (rows with more than 5 containers after the others when they are 1-50 % of
  * a batch of >= 2^18 rows and hold >= 30 % of its containers; KW_SPLIT=0 / 1 never / always) — as a

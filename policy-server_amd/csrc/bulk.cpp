@@ -333,7 +333,7 @@ struct BulkPass {
     const auto td = clk::now();
     cd.clear();
     co.assign(1, 0u);
-    if (int rc = build_descs(kb->b, pl.geom, 0, kb->b.n, tb[k], tb[k + 1], 128, &cd, &co)) return rc;
+    if (int rc = build_descs(kb->b, pl.geom, 0, kb->b.n, tb[k], tb[k + 1], 128, 0, &cd, &co)) return rc;  // (fixed cut: pass.cpp)
     co[0] = (uint32_t)(co.size() - 1);
     if (cd.size() > dcap) {  // more split tiles than the halves hold: wait for every launch, regrow
       HIPCHK(hipStreamSynchronize(res->s_in.s));

@@ -591,7 +591,7 @@ int kw_debug_copy_jobs(const kw_env* env, kw_batch* kb, const int32_t* policies,
       std::vector<TileDesc> desc;
       std::vector<uint32_t> ovf;
       const uint64_t ntiles = (rg.hi - rg.lo + T.rows - 1) / T.rows;
-      if ((rc = build_descs(B, T, rg.lo, rg.hi, 0, ntiles, 4096, &desc, &ovf))) break;
+      if ((rc = build_descs(B, T, rg.lo, rg.hi, 0, ntiles, 4096, rg.grid, &desc, &ovf))) break;
       for (uint32_t v : {T.rows, T.njobs, (uint32_t)desc.size(), (uint32_t)ovf.size(), (uint32_t)rg.lo, (uint32_t)rg.hi, T.lds_bytes,
                          (uint32_t)D.split})
         w.push_back(v);
@@ -624,6 +624,65 @@ int kw_debug_copy_jobs(const kw_env* env, kw_batch* kb, const int32_t* policies,
   *needed = w.size();
   if (cap < w.size()) return KW_E_NOSPACE;
   std::copy(w.begin(), w.end(), out);
+  return KW_OK;
+}
+
+int kw_debug_tile_descs(const kw_env* env, kw_batch* kb, const int32_t* policies, uint32_t npol, int origin, uint32_t* out,
+                        size_t cap, size_t* needed) {
+  if (!env || !kb || !needed || (!out && cap) || (!policies && npol)) return KW_E_ARG;
+  std::unique_ptr<DeviceBatch> saved = std::move(kb->dev);
+  kb->dev = host_view(kb);
+  const Batch& B = dev_rows(kb);
+  PassPlan plan;
+  int rc = plan_pass(env, kb, policies, npol, nullptr, origin, false, &plan);
+  std::vector<uint32_t> w;
+  if (rc == KW_OK) {
+    std::vector<TileDesc> desc;
+    std::vector<uint32_t> ovf;
+    uint64_t at[2] = {0, 0}, nd[2] = {0, 0};
+    rc = plan_descs(B, plan, &desc, &ovf, at, nd);  // what a resident pass uploads
+    if (rc == KW_OK) {
+      w.push_back((uint32_t)plan.regions.size());
+      w.push_back(ovf[0]);
+      for (size_t k = 0; k < plan.regions.size(); ++k) {
+        const PassPlan::Region& rg = plan.regions[k];
+        const TileArgs& T = rg.geom;
+        const TileCostW W = tile_cost_weights(T.feat, T.need);
+        for (uint32_t v : {T.rows, T.cmax, T.kmax, T.lmax, rg.grid, tile_slot(nd[k], rg.grid, 0).nx, rg.dyn ? 1u : 0u,
+                           (uint32_t)nd[k], (uint32_t)rg.lo, (uint32_t)rg.hi})
+          w.push_back(v);
+        for (int m = 0; m < (int)NSTR; ++m) w.push_back(T.o_sb[m] ? 1u : 0u);
+        w.insert(w.end(), T.sb_cap, T.sb_cap + NSTR);
+        for (uint64_t i = at[k]; i < at[k] + nd[k]; ++i) {
+          const uint32_t* dw = (const uint32_t*)&desc[i];
+          w.insert(w.end(), dw, dw + sizeof(TileDesc) / 4);
+          const uint64_t c = desc_cost(W, desc[i]);
+          w.push_back((uint32_t)c);
+          w.push_back((uint32_t)(c >> 32));
+        }
+      }
+      w.insert(w.end(), ovf.begin() + 1, ovf.end());
+    }
+  }
+  kb->dev->verdicts = nullptr;  // host memory: not the DeviceBatch's to free
+  kb->dev = std::move(saved);
+  if (rc) return rc;
+  *needed = w.size();
+  if (cap < w.size()) return KW_E_NOSPACE;
+  std::copy(w.begin(), w.end(), out);
+  return KW_OK;
+}
+
+uint64_t kw_debug_tile_cost(uint32_t feat, uint32_t need, uint32_t requests, uint32_t labels, uint32_t containers,
+                            uint32_t capabilities) {
+  return tile_cost(tile_cost_weights(feat, need), requests, labels, containers, capabilities);
+}
+
+int kw_debug_tile_slot(uint64_t ndesc, uint32_t grid, uint32_t workgroup, uint32_t tile, uint64_t* out) {
+  if (!out || !grid || workgroup >= grid) return KW_E_ARG;
+  const TileSlot s = tile_slot(ndesc, grid, workgroup);
+  const uint64_t v[7] = {s.nx, s.xcd, s.slot, s.wpx, s.t_lo, s.t_hi, tile_at(s, tile)};
+  std::copy(v, v + 7, out);
   return KW_OK;
 }
 

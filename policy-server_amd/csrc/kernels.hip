@@ -569,6 +569,9 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   // P0 and its L2 prefetch read it there, with no dependent global load), and the counter fetch
   // issued now names the tile after next.
   const bool dyn = a.sched != nullptr;
+  // (kernels.hpp tile_slot states this arithmetic for the host, which counts a slot's tiles by it
+  // when it cuts them. The kernel keeps its own statements: computed through the helper's struct
+  // every instantiation spilled two more SGPRs and C2 ran 1 % slower, profiles/r08_tile_cuts_ab.txt.)
   const uint32_t nx = min(8u, gridDim.x);
   const uint32_t xcd = blockIdx.x % nx;
   // both schedules serve the XCD's contiguous range (adjacent tiles share the cache lines at their
@@ -1382,6 +1385,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   }
   if (timing && tid == 0) {  // one lane's vector stores
     ph[6] = clock64() - t_begin;
+    a.phase[(uint64_t)blockIdx.x * kPhaseWords + 8u + SG_END] = __builtin_amdgcn_s_memrealtime();
     for (int k = 0; k < 8; ++k) a.phase[(uint64_t)blockIdx.x * kPhaseWords + (uint32_t)k] = ph[k];
   }
   if (dyn && tid == 0) {  // the XCD's last workgroup (every other one has taken its last tile) resets

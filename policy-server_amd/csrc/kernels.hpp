@@ -59,9 +59,13 @@ enum Seg : uint32_t {
   // P0 issue: tile loop top to the descriptor's `fits`; the jobs' spans (copy_span on every lane); the
   // wave's job loop (readlanes and copies)
   SG_P0_TOP, SG_P0_REQ, SG_P0_STR,
-  kSegWords = 19
+  SG_END,  // the workgroup's end after its last tile (s_memrealtime): how evenly an XCD's slots finish
+  kSegWords = 20
 };
-constexpr uint32_t kPhaseWords = 8 + kSegWords;
+// A workgroup's words fill whole 128-byte lines: neighbouring workgroups run on different XCDs, and
+// so no two L2s hold the same line of counters.
+constexpr uint32_t kPhaseWords = 32;
+static_assert(kPhaseWords >= 8 + kSegWords && kPhaseWords % 16 == 0, "phase words per workgroup: whole lines");
 
 // Slot kernel geometry: one tile = up to 64 requests (one lane per request where a lane walks a
 // request), 256 threads.
@@ -207,6 +211,61 @@ struct alignas(16) TileDesc {
   uint32_t pad[4];
 };
 static_assert(sizeof(TileDesc) == 128, "TileDesc layout");
+
+// The tile schedule's index arithmetic, one statement of it for the kernel and for the host, which
+// counts a launch's tiles per slot by it (pass.cpp build_descs): workgroup b of a grid runs on XCD b % nx and is that XCD's slot
+// b / nx; the XCD serves the contiguous descriptors [t_lo, t_hi) of the launch's ndesc, and on the
+// strided schedule slot j's k-th tile is the descriptor at t_lo + j + k * wpx.
+struct TileSlot {
+  uint32_t nx, xcd, slot, wpx;  // XCDs in use; the workgroup's XCD and slot in it; the XCD's workgroups
+  uint64_t t_lo, t_hi;
+};
+KW_HD inline TileSlot tile_slot(uint64_t ndesc, uint32_t grid, uint32_t b) {
+  TileSlot s;
+  s.nx = grid < 8u ? grid : 8u;
+  s.xcd = b % s.nx;
+  s.slot = b / s.nx;
+  s.wpx = (grid - s.xcd + s.nx - 1u) / s.nx;  // workgroups b < grid with b % nx == xcd
+  s.t_lo = ndesc * s.xcd / s.nx;
+  s.t_hi = ndesc * (s.xcd + 1u) / s.nx;
+  return s;
+}
+// The descriptor a slot runs as its k-th tile on the strided schedule (a tile only while < t_hi).
+KW_HD inline uint64_t tile_at(const TileSlot& s, uint32_t k) { return s.t_lo + s.slot + (uint64_t)k * s.wpx; }
+
+// Estimated cost of a tile in wave-cycles, from its item counts: P1 and P2 run their items in
+// 64-lane blocks, one wave a block, and a block costs its longest chain however few lanes it fills
+// (DESIGN.md §5), so a segment costs per block, not per item. The planner cuts tiles where the cost
+// per request is least (pass.cpp build_descs).
+struct TileCostW {
+  uint32_t fixed, req, lbl, ctr, cap;  // per tile; per block of requests / labels / containers / capability strings
+};
+KW_HD constexpr uint32_t tile_blocks(uint32_t items) { return (items + 63u) / 64u; }
+KW_HD constexpr uint64_t tile_cost(const TileCostW& w, uint32_t nreq, uint32_t nlbl, uint32_t nctr, uint32_t ncap) {
+  return (uint64_t)w.fixed + (uint64_t)w.req * tile_blocks(nreq) + (uint64_t)w.lbl * tile_blocks(nlbl) +
+         (uint64_t)w.ctr * tile_blocks(nctr) + (uint64_t)w.cap * tile_blocks(ncap);
+}
+// The weights of a launch's family set (TileArgs::feat) and classified string columns (need).
+// Label / container families (C4's instantiation), from the committed segment clocks of
+// profiles/r07_p0_segments.txt ("change" rows: cycles per wave and tile, x 4 waves, over the mean
+// blocks per tile of that batch — 4.07 label, 2.47 container, 3.47 capability-string, 1 request):
+//   label    (P1 label 7435 + P2 label 2702) x 4 / 4.07 =  9.96 k
+//   ctr      (P1 ctr   1758 + P2 ctr   4790) x 4 / 2.47 = 10.6 k
+//   cap       P1 capstr 2382                 x 4 / 3.47 =  2.75 k
+//   request  (P1 req    646 + P2 req   1467) x 4        =  8.45 k
+//   fixed     tile 32950 x 4 less the four segments above = 47.0 k
+// The r08 refit on two other boxes (profiles/r08_tile_cost_fit.txt) gave each within 0.3 % and
+// within 6 % (that box's clocks run 2.7 % higher throughout); the weights stay.
+// Image family: a container also costs its image chain in P1; profiles/r03_segment_clocks.txt, C2:
+// (P1 image 18020 + P2 ctr 3960) x 4 / 2.47 = 35.6 k per container block.
+KW_HD constexpr TileCostW tile_cost_weights(uint32_t feat, uint32_t need) {
+  TileCostW w{47000u, 8450u, 0u, 0u, 0u};
+  if ((feat & kFeatLbl) && (need & (1u << S_LK))) w.lbl = 9960u;
+  if (feat & kFeatCtr) w.ctr = 10600u;
+  if ((feat & kFeatCtr) && (need & (1u << S_CAPADD))) w.cap = 2750u;
+  if ((feat & kFeatImg) && (need & (1u << S_IMG))) w.ctr = 35600u;
+  return w;
+}
 
 // Fills T->jobs / njobs (plan.cpp) from T's LDS layout and string columns and the batch's six
 // request / container arrays cols[] = {req_flags, ctr_off, lbl_off, ctr_flags, capadd_off, capdrop_off}.

@@ -23,7 +23,7 @@ int upload_env(kw_env* env, int device) {
 }
 
 int build_descs(const Batch& B, const TileArgs& T, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t t1, uint64_t range,
-                std::vector<TileDesc>* desc, std::vector<uint32_t>* ovf) {
+                uint32_t grid, std::vector<TileDesc>* desc, std::vector<uint32_t>* ovf) {
   // descriptor of requests [r0, r1); false when it exceeds the capacities
   auto make = [&](uint64_t r0, uint64_t r1, TileDesc* dp) {
     TileDesc& d = *dp;
@@ -52,38 +52,116 @@ int build_descs(const Batch& B, const TileArgs& T, uint64_t lo, uint64_t hi, uin
     d.fits = fits ? 1u : 0u;
     return fits;
   };
+  // Block-aware cuts (KW_TILE_CUT, on by default): a tile from row r may end at any row of
+  // [r + rows - rows / 8, r + rows], and ends where its estimated cost (kernels.hpp tile_cost) per
+  // row is least, the longer tile on a tie: P1 and P2 pay per 64-item block, so a tile that stops
+  // just before a segment spills into a nearly empty block does the same rows' work for a block
+  // less. What is left of a range once it fits one tile stays one tile (two would pay the fixed
+  // cost twice for no block saved). Off: every tile is `rows` tall, as before r08.
+  // The choice is greedy, tile by tile, and each cut hands the rows it left out to the next tile, so
+  // it is checked against the fixed cut twice. Per range: the cut descriptors are kept only where
+  // their estimated cost sums to less than the fixed ones' (short tiles whose blocks are far from
+  // full, 24-row ones for C4, gain nothing and pay the per-tile cost more often). Per call: the cuts
+  // make ~2 % more tiles, and where that gives an XCD's busiest slot a tile more than the fixed cut
+  // does (a launch of few tiles a slot, such as a small shard), a slot's extra tile costs more than
+  // every tile's saved block; the fixed cut stays.
+  // Not cut (profiles/r08_tile_cuts_ab.txt): launches of the image families alone (C2 / C3: no
+  // block weights were fitted for them and the cuts measured +0.5 % at C2), and the bulk path's
+  // per-chunk descriptors (grid 0: their build is on the pipeline's critical path, the cut build
+  // costs 2-3 x the fixed one, and a chunk of whole rounds would not keep its cuts anyway).
+  const bool cut = Knobs::on<KW_TILE_CUT>() && grid && (T.feat & (kFeatLbl | kFeatCtr));
+  const TileCostW W = tile_cost_weights(T.feat, T.need);
+  auto cost = [&](uint64_t r0, uint64_t r1) {
+    const uint32_t cb = B.ctr_off[r0], ce = B.ctr_off[r1];
+    return tile_cost(W, (uint32_t)(r1 - r0), B.lbl_off[r1] - B.lbl_off[r0], ce - cb,
+                     (B.capadd_off[ce] - B.capadd_off[cb]) + (B.capdrop_off[ce] - B.capdrop_off[cb]));
+  };
   const size_t nq = (size_t)((t1 - t0 + range - 1) / range);
-  std::vector<std::vector<TileDesc>> qdesc(nq);
-  std::vector<std::vector<uint32_t>> qovf(nq);
+  // [0]: the fixed cut, [1]: the block-aware one
+  std::vector<std::vector<TileDesc>> qdesc[2] = {std::vector<std::vector<TileDesc>>(nq), std::vector<std::vector<TileDesc>>(nq)};
+  std::vector<std::vector<uint32_t>> qovf[2] = {std::vector<std::vector<uint32_t>>(nq), std::vector<std::vector<uint32_t>>(nq)};
+  std::vector<uint8_t> qcut(nq, 0);  // the range keeps its cut descriptors
   std::atomic<bool> too_far{false};
   HostWorkers::get().run(nq, [&](size_t q) {
     std::vector<std::pair<uint64_t, uint64_t>> todo;
-    std::vector<TileDesc>& dv = qdesc[q];
-    dv.reserve((size_t)range + range / 64);
-    for (uint64_t tile = t0 + q * range, te = std::min<uint64_t>(t1, t0 + (q + 1) * range); tile < te; ++tile) {
-      todo.assign(1, {lo + tile * T.rows, std::min<uint64_t>(hi, lo + (tile + 1) * T.rows)});
-      while (!todo.empty()) {
-        const auto [r0, r1] = todo.back();
-        todo.pop_back();
-        TileDesc d;
-        if (make(r0, r1, &d)) {
-          dv.push_back(d);
-        } else if (r1 - r0 > 1) {
-          const uint64_t mid = r0 + (r1 - r0) / 2;
-          todo.push_back({mid, r1});
-          todo.push_back({r0, mid});
-        } else {
-          if (r0 > 0xffffffffull) too_far = true;  // overflow list holds u32 request indices
-          qovf[q].push_back((uint32_t)r0);
+    // the range's rows: the cuts are independent per range, so the ranges build in parallel and a
+    // range's last tile is simply shorter
+    const uint64_t qb = lo + (t0 + q * range) * T.rows;
+    const uint64_t qe = std::min<uint64_t>(hi, lo + std::min<uint64_t>(t1, t0 + (q + 1) * range) * T.rows);
+    uint64_t total[2] = {0, 0};
+    for (int v = 0; v <= (cut ? 1 : 0); ++v) {
+      std::vector<TileDesc>& dv = qdesc[v][q];
+      dv.reserve((size_t)range + (v ? range / 8 : 0) + range / 64 + 1);
+      for (uint64_t r = std::min(qb, qe); r < qe;) {
+        uint64_t end = std::min<uint64_t>(qe, r + T.rows);
+        if (v && end < qe) {
+          uint64_t best = cost(r, end);
+          for (uint64_t e = end - 1; e >= r + T.rows - T.rows / 8 && e > r; --e) {
+            const uint64_t c = cost(r, e);
+            if (c * (end - r) < best * (e - r)) best = c, end = e;  // c / (e - r) < best / (end - r)
+          }
+        }
+        todo.assign(1, {r, end});
+        r = end;
+        while (!todo.empty()) {
+          const auto [r0, r1] = todo.back();
+          todo.pop_back();
+          TileDesc d;
+          if (make(r0, r1, &d)) {
+            dv.push_back(d);
+            total[v] += desc_cost(W, d);
+          } else if (r1 - r0 > 1) {
+            const uint64_t mid = r0 + (r1 - r0) / 2;
+            todo.push_back({mid, r1});
+            todo.push_back({r0, mid});
+          } else {
+            if (r0 > 0xffffffffull) too_far = true;  // overflow list holds u32 request indices
+            qovf[v][q].push_back((uint32_t)r0);
+          }
         }
       }
     }
+    qcut[q] = cut && total[1] < total[0];
   });
   if (too_far) return KW_E_ARG;
-  for (size_t q = 0; q < nq; ++q) {
-    desc->insert(desc->end(), qdesc[q].begin(), qdesc[q].end());
-    ovf->insert(ovf->end(), qovf[q].begin(), qovf[q].end());
+  if (cut) {
+    uint64_t n[2] = {0, 0};
+    for (size_t q = 0; q < nq; ++q) n[0] += qdesc[0][q].size(), n[1] += qdesc[qcut[q]][q].size();
+    auto rounds = [&](uint64_t nd) {  // tiles of the busiest slot (kernels.hpp tile_slot)
+      uint64_t most = 0;
+      for (uint32_t x = 0; x < tile_slot(nd, grid, 0).nx; ++x) {
+        const TileSlot ts = tile_slot(nd, grid, x);
+        most = std::max(most, (ts.t_hi - ts.t_lo + ts.wpx - 1) / ts.wpx);
+      }
+      return most;
+    };
+    if (rounds(n[1]) > rounds(n[0])) std::fill(qcut.begin(), qcut.end(), 0);
   }
+  for (size_t q = 0; q < nq; ++q) {
+    desc->insert(desc->end(), qdesc[qcut[q]][q].begin(), qdesc[qcut[q]][q].end());
+    ovf->insert(ovf->end(), qovf[qcut[q]][q].begin(), qovf[qcut[q]][q].end());
+  }
+  return KW_OK;
+}
+
+uint64_t desc_cost(const TileCostW& w, const TileDesc& d) {
+  return d.fits ? tile_cost(w, d.nr, d.le - d.lb, d.ce - d.cb, (d.kae - d.kab) + (d.kde - d.kdb)) : 0;
+}
+
+int plan_descs(const Batch& B, const PassPlan& plan, std::vector<TileDesc>* desc, std::vector<uint32_t>* ovf, uint64_t at[2],
+               uint64_t nd[2]) {
+  desc->clear();
+  ovf->assign(1, 0u);
+  if (plan.regions.size() > 2) return KW_E_ARG;
+  for (size_t k = 0; k < plan.regions.size(); ++k) {  // region k's descriptors after region k-1's; one overflow list
+    const PassPlan::Region& rg = plan.regions[k];
+    const uint64_t ntiles = (rg.hi - rg.lo + rg.geom.rows - 1) / rg.geom.rows;
+    at[k] = desc->size();
+    desc->reserve(desc->size() + ntiles + ntiles / 8 + ntiles / 64 + 1);
+    if (int rc = build_descs(B, rg.geom, rg.lo, rg.hi, 0, ntiles, 4096, rg.grid, desc, ovf)) return rc;
+    nd[k] = desc->size() - at[k];
+  }
+  (*ovf)[0] = (uint32_t)(ovf->size() - 1);
   return KW_OK;
 }
 
@@ -92,10 +170,14 @@ int build_descs(const Batch& B, const TileArgs& T, uint64_t lo, uint64_t hi, uin
 static int upload_tile_descs(const Batch& B, DeviceBatch* D, const PassPlan& plan, hipStream_t s) {
   uint64_t key = 1469598103934665603ull;
   auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
+  mix(Knobs::on<KW_TILE_CUT>());
   for (const PassPlan::Region& rg : plan.regions) {
     const TileArgs& T = rg.geom;
     mix(rg.lo);
     mix(rg.hi);
+    mix(rg.grid);  // the cuts are kept only where they cost this grid's busiest slot no tile more
+    mix(T.feat);   // the cost weights
+    mix(T.need);
     mix(T.rows);
     mix(T.cmax);
     mix(T.kmax);
@@ -109,18 +191,9 @@ static int upload_tile_descs(const Batch& B, DeviceBatch* D, const PassPlan& pla
   const bool dbg = Knobs::on<KW_BULK_DEBUG>();  // diagnostics
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<TileDesc> desc;
-  std::vector<uint32_t> ovf{0};
-  if (plan.regions.size() > 2) return KW_E_ARG;
+  std::vector<uint32_t> ovf;
   uint64_t at[2] = {0, 0}, nd[2] = {0, 0};
-  for (size_t k = 0; k < plan.regions.size(); ++k) {  // region k's descriptors after region k-1's; one overflow list
-    const PassPlan::Region& rg = plan.regions[k];
-    const uint64_t ntiles = (rg.hi - rg.lo + rg.geom.rows - 1) / rg.geom.rows;
-    at[k] = desc.size();
-    desc.reserve(desc.size() + ntiles + ntiles / 64 + 1);
-    if (int rc = build_descs(B, rg.geom, rg.lo, rg.hi, 0, ntiles, 4096, &desc, &ovf)) return rc;
-    nd[k] = desc.size() - at[k];
-  }
-  ovf[0] = (uint32_t)(ovf.size() - 1);
+  if (int rc = plan_descs(B, plan, &desc, &ovf, at, nd)) return rc;
   const auto t1 = std::chrono::steady_clock::now();
   HIPCHK(hipStreamSynchronize(s));  // a running pass may still read the previous descriptors
   D->h_desc = std::move(desc);
@@ -332,6 +405,33 @@ static void print_phase_report(size_t launch, uint32_t grid, const std::vector<u
   }
   fprintf(stderr, "[kw start] launch %zu: %u of %u workgroups started > 20 us after their XCD's first (widest spread %.1f us)\n",
           launch, late, grid, spread);
+  // workgroup end times, per XCD as above: the spread between the first and the last slot to finish,
+  // and the share of slot-time (slots x the XCD's span from its first start to its last end) that
+  // slots stand idle after their own end
+  fprintf(stderr, "[kw finish] launch %zu: per XCD end spread us / idle share:", launch);
+  double idle_all = 0, span_all = 0;
+  uint32_t stamped = 0;
+  for (uint32_t x = 0; x < nx; ++x) {
+    uint64_t first = ~0ull, e_lo = ~0ull, e_hi = 0, n = 0, ends = 0;
+    for (uint32_t q = x; q < grid; q += nx) {
+      const uint64_t* w = &ph[(size_t)q * kPhaseWords + 8];
+      if (!w[SG_START] || !w[SG_END]) continue;  // (a stamp that did not arrive)
+      ++n;
+      first = std::min(first, w[SG_START]);
+      e_lo = std::min(e_lo, w[SG_END]);
+      e_hi = std::max(e_hi, w[SG_END]);
+      ends += w[SG_END];
+    }
+    const double idle = (double)n * (double)e_hi - (double)ends, span = (double)n * (double)(e_hi - first);
+    idle_all += idle;
+    span_all += span;
+    stamped += (uint32_t)n;
+    fprintf(stderr, " %.1f / %.1f %%", (double)(e_hi - e_lo) / 100.0, span > 0 ? 100.0 * idle / span : 0.0);
+  }
+  // (r08: every fourth workgroup's start stamp reads back zero at grid 1024, which is also why
+  // [kw start] counts 768 late there; cause not found, those workgroups are left out here)
+  fprintf(stderr, " (all: %.1f %% idle; %u of %u workgroups stamped)\n", span_all > 0 ? 100.0 * idle_all / span_all : 0.0,
+          stamped, grid);
 }
 
 // One pass: prepare, the optional NFA pre-pass, the per-region launches, the overflow launch.

@@ -39,8 +39,23 @@ int upload_env(kw_env* env, int device);
 // The descriptors of tiles [t0, t1) of geometry T over rows [lo, hi), in row order, and the requests that exceed the
 // capacities alone (overflow); a run that does not fit is halved until its parts do. Tiles in ranges
 // of `range` on the host workers. KW_E_ARG when an overflow request index exceeds u32.
+// [t0, t1) counts tiles of the full height T.rows, which fixes the rows covered; with KW_TILE_CUT
+// (the default) a range's rows are cut into tiles of [rows - rows / 8, rows] rows each, at the least
+// estimated cost per row, so a range gives up to 1/8 more descriptors than tiles. A range keeps the
+// fixed cut where that is the cheaper, and the whole call does where the cuts would give the busiest
+// slot of a launch of `grid` workgroups over these descriptors a tile more. grid 0 (the bulk path's
+// per-chunk descriptors) and launches of the image families alone: the fixed cut.
 int build_descs(const Batch& B, const TileArgs& T, uint64_t lo, uint64_t hi, uint64_t t0, uint64_t t1, uint64_t range,
-                std::vector<TileDesc>* desc, std::vector<uint32_t>* ovf);
+                uint32_t grid, std::vector<TileDesc>* desc, std::vector<uint32_t>* ovf);
+
+// A descriptor's estimated cost (kernels.hpp tile_cost over its item counts); one the host queued
+// for the overflow kernels (fits == 0) costs the tile kernel nothing.
+uint64_t desc_cost(const TileCostW& w, const TileDesc& d);
+
+// A resident pass's descriptors, region after region (at[k], nd[k]: region k's place and count),
+// cut by build_descs, in row order; one overflow list ([count, rows...]).
+int plan_descs(const Batch& B, const PassPlan& plan, std::vector<TileDesc>* desc, std::vector<uint32_t>* ovf, uint64_t at[2],
+               uint64_t nd[2]);
 
 // Per-string class arrays of the overflow path (absolute entity indices), one allocation.
 int ensure_overflow_classes(const Batch& B, DeviceBatch* D, const TileArgs& T, EvalArgs* A);

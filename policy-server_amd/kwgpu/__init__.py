@@ -431,6 +431,22 @@ class Batch:
         raise_for(rc, "kw_debug_copy_jobs failed")
         return out[:need.value]
 
+    def debug_tile_descs(self, env, policies, origin=VALIDATE):
+        """Diagnostic (kw_debug_tile_descs): the tile descriptors a resident all-pairs pass would
+        upload, cut per tile at the least estimated cost per row, planned on the host, as a uint32
+        array (layout: include/kwgpu.h)."""
+        import numpy as np
+        arr = env._array(policies)
+        need = C.c_size_t()
+        rc = self._L.kw_debug_tile_descs(env._h, self._h, arr, len(policies), origin, None, 0, C.byref(need))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_debug_tile_descs failed")
+        out = np.zeros(max(need.value, 1), dtype=np.uint32)
+        rc = self._L.kw_debug_tile_descs(env._h, self._h, arr, len(policies), origin,
+                                         out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(need))
+        raise_for(rc, "kw_debug_tile_descs failed")
+        return out[:need.value]
+
     def debug_reorder(self):
         """Diagnostic (kw_debug_reorder): the device-row order kw_batch_to_device gives this batch,
         as (batch in that order, perm, light-region rows); perm[d] is the batch row at device row d."""
