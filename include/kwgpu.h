@@ -338,6 +338,52 @@ int kw_batch_verdicts(kw_batch *b, uint32_t *host_out, size_t count);
  * for a bulk caller, the per-request loop of acquire_semaphore_and_evaluate (handlers.rs:256-286). */
 int kw_validate_host(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
                      int device, uint32_t *out, size_t count, uint32_t chunk_rows);
+/* The packed verdict form of a pass of rows x npol: lossless, for bulk callers whose read-back is
+ * the longer direction. A word without a violation depends only on its column (the
+ * policy's mode and allowedToMutate, the origin) and on whether the response mutated or the request
+ * was bypassed, so each (row, column) is a 2-bit code into a three-word dictionary per column, and
+ * only the other words are stored. With G = ceil(npol / 64) column groups, all arrays caller-owned:
+ *   dict     u32[npol][3]: the column's word for an accepted response, for an accepted and mutated
+ *            one, and for a bypassed request (a column whose word is the same whatever the request
+ *            holds that word first). A fixed function of (env, policies, origin).
+ *   planes   u64[rows][G][2]: bit c of planes[r][g][0] / [1] is the low / high bit of the code of
+ *            column 64 g + c. Codes 0-2: the word is dict[col][code] (the lowest matching index);
+ *            code 3: the word is an exception. Bits of columns >= npol are 0.
+ *   exc_off  u32[rows + 1]: exc_off[r] is the index in exc of row r's first exception, exc_off[rows]
+ *            the total.
+ *   exc      u32[exc_cap]: the exception words in (row, column) order: the word of (r, col) is
+ *            exc[exc_off[r] + the number of code-3 columns of row r below col].
+ *   exc_count (output) the exception words of the pass.
+ * The same input gives the same bytes. No reference counterpart (an output form of the bulk entry). */
+typedef struct kw_packed {
+  uint64_t rows;
+  uint32_t npol;
+  uint64_t *planes;
+  uint32_t *exc_off;
+  uint32_t *exc;
+  size_t exc_cap;
+  uint32_t *dict;
+  size_t exc_count;
+} kw_packed;
+/* kw_validate_host with the verdicts in the packed form: out->rows, npol, the five pointers and
+ * exc_cap come from the caller (rows = the batch's, npol = the list's, else KW_E_ARG; so is a pass of
+ * rows x npol >= 2^32). The device packs each chunk's words behind its kernels and only the planes,
+ * the offsets and the exceptions are read back. Direct DMA when planes, exc_off and exc are all
+ * page-locked (kw_host_alloc), else through pinned bounce blocks. When the exceptions exceed exc_cap
+ * the pass still runs to its end: KW_E_NOSPACE with the need in out->exc_count, the arrays' contents
+ * then unspecified. kw_batch_wide_arg and kw_batch_group_causes work after it as after
+ * kw_validate_host. */
+int kw_validate_host_packed(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
+                            int device, kw_packed *out, uint32_t chunk_rows);
+/* The verdict word of (row, col) of a packed pass; KW_E_ARG outside it. */
+int kw_packed_word(const kw_packed *p, uint64_t row, uint32_t col, uint32_t *word);
+/* Rows [row0, row1) of a packed pass as full words, out [row1 - row0][npol]. */
+int kw_packed_unpack(const kw_packed *p, uint64_t row0, uint64_t row1, uint32_t *out);
+/* Diagnostic (tests, documents): full words [rows][npol] into the packed form on the host, by the
+ * reference encoder under the dictionary a device pass over (env, policies, origin) uses. out as
+ * for kw_validate_host_packed (rows from the caller); KW_E_NOSPACE likewise. */
+int kw_debug_pack_words(const kw_env *env, const int32_t *policies, uint32_t npol, int origin, const uint32_t *words,
+                        uint64_t rows, kw_packed *out);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes

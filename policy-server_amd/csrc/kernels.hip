@@ -1834,6 +1834,156 @@ hipError_t launch_scatter(const ScatterArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- packed verdict output (kernels.hpp PackArgs, packed.hpp) -----------------------------------
+
+// What a lane holds in round t of a pack kernel's wave: its item, and its column when it holds one.
+struct PackLane {
+  uint64_t item, row;
+  uint32_t col, c, sub;
+  bool on;
+};
+__device__ inline PackLane pack_lane(const PackArgs& a, const PackGeom& g, uint64_t item0, uint32_t t, uint32_t lane) {
+  PackLane L;
+  L.sub = lane / g.w;
+  L.c = lane % g.w;
+  L.item = item0 + (uint64_t)t * g.ipi + L.sub;
+  const uint32_t grp = a.G == 1u ? 0u : (uint32_t)(L.item % a.G);
+  L.row = a.G == 1u ? L.item : L.item / a.G;
+  L.col = 64u * grp + L.c;
+  L.on = L.sub < g.ipi && L.item < a.nitems && L.col < a.npol;
+  return L;
+}
+
+__global__ void __launch_bounds__(256) pack_codes_kernel(PackArgs a) {
+  const PackGeom g = pack_geom(a.npol);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t item0 = ((((uint64_t)blockIdx.x * 256u) + threadIdx.x) >> 6) * g.ipw;  // wave-uniform
+  if (item0 >= a.nitems) return;
+  const uint64_t mask = g.w == 64u ? ~0ull : (1ull << g.w) - 1ull;
+  uint32_t d0 = 0, d1 = 0, d2 = 0, dcol = ~0u;  // the lane's column's dictionary
+  uint64_t my_lo = 0, my_hi = 0;
+  for (uint32_t t = 0; t < g.T; ++t) {
+    const PackLane L = pack_lane(a, g, item0, t, lane);
+    uint32_t code = 0;
+    if (L.on) {
+      if (L.col != dcol) {  // (only passes of more than 64 columns change a lane's column)
+        dcol = L.col;
+        d0 = a.dict[3u * dcol], d1 = a.dict[3u * dcol + 1u], d2 = a.dict[3u * dcol + 2u];
+      }
+      code = packed_code(a.words[L.row * a.npol + L.col], d0, d1, d2);
+    }
+    const uint64_t blo = __ballot(code & 1u), bhi = __ballot(code >> 1);
+    const uint32_t j = lane - t * g.ipi;  // lane t * ipi + j keeps the round's item j
+    if (lane >= t * g.ipi && j < g.ipi) {
+      my_lo = (blo >> (j * g.w)) & mask;
+      my_hi = (bhi >> (j * g.w)) & mask;
+    }
+  }
+  if (lane < g.ipw && item0 + lane < a.nitems) {
+    *(ulonglong2*)(a.planes + 2u * (item0 + lane)) = make_ulonglong2(my_lo, my_hi);
+    a.ibase[item0 + lane] = packed_popc(my_lo & my_hi);
+  }
+}
+
+// Exclusive scan of v over the workgroup's 256 threads (*total: their sum); lds: 4 words.
+__device__ inline uint32_t block_scan256(uint32_t v, uint32_t* lds, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t x = v;
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint32_t y = __shfl_up(x, d);
+    if (lane >= d) x += y;
+  }
+  __syncthreads();  // (lds may still be read from a previous call)
+  if (lane == 63u) lds[wave] = x;
+  __syncthreads();
+  uint32_t base = 0, sum = 0;
+  for (uint32_t q = 0; q < 4u; ++q) {
+    if (q < wave) base += lds[q];
+    sum += lds[q];
+  }
+  *total = sum;
+  return base + x - v;
+}
+
+__global__ void __launch_bounds__(256) pack_sums_kernel(PackArgs a) {
+  __shared__ uint32_t lds[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x * kScanPer;
+  uint32_t s = 0;
+  for (uint32_t q = 0; q < kScanPer; ++q)
+    if (i0 + q < a.nitems) s += a.ibase[i0 + q];
+  uint32_t total;
+  (void)block_scan256(s, lds, &total);
+  if (threadIdx.x == 0) a.bsum[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(256) pack_scan_kernel(PackArgs a, uint32_t nblocks) {  // one workgroup
+  __shared__ uint32_t lds[4];
+  uint32_t carry = a.tot[0];
+  for (uint32_t b0 = 0; b0 < nblocks; b0 += 256u) {
+    const uint32_t b = b0 + threadIdx.x;
+    uint32_t total;
+    const uint32_t ex = block_scan256(b < nblocks ? a.bsum[b] : 0u, lds, &total);
+    if (b < nblocks) a.bsum[b] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    a.tot[1] = carry;
+    a.exc_off[a.nitems / a.G] = carry;
+  }
+}
+
+__global__ void __launch_bounds__(256) pack_bases_kernel(PackArgs a) {
+  __shared__ uint32_t lds[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x * kScanPer;
+  uint32_t c[kScanPer], s = 0;
+  for (uint32_t q = 0; q < kScanPer; ++q) {
+    c[q] = i0 + q < a.nitems ? a.ibase[i0 + q] : 0u;
+    s += c[q];
+  }
+  uint32_t total;
+  uint32_t at = a.bsum[blockIdx.x] + block_scan256(s, lds, &total);
+  for (uint32_t q = 0; q < kScanPer; ++q) {
+    const uint64_t i = i0 + q;
+    if (i < a.nitems) {
+      a.ibase[i] = at;
+      if (a.G == 1u) a.exc_off[i] = at;
+      else if (i % a.G == 0) a.exc_off[i / a.G] = at;
+    }
+    at += c[q];
+  }
+}
+
+__global__ void __launch_bounds__(256) pack_scatter_kernel(PackArgs a) {
+  const PackGeom g = pack_geom(a.npol);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t item0 = ((((uint64_t)blockIdx.x * 256u) + threadIdx.x) >> 6) * g.ipw;
+  if (item0 >= a.nitems) return;
+  const uint32_t seed = a.tot[0];
+  for (uint32_t t = 0; t < g.T; ++t) {
+    const PackLane L = pack_lane(a, g, item0, t, lane);
+    if (!L.on) continue;
+    const ulonglong2 pl = *(const ulonglong2*)(a.planes + 2u * L.item);
+    const uint64_t esc = pl.x & pl.y;
+    if (!((esc >> L.c) & 1ull)) continue;
+    const uint32_t at = a.ibase[L.item] - seed + packed_popc(esc & packed_below(L.c));
+    if (at < a.exc_cap) a.exc[at] = a.words[L.row * a.npol + L.col];
+  }
+}
+
+hipError_t launch_pack(const PackArgs& a, hipStream_t s) {
+  if (a.nitems == 0) return hipSuccess;
+  const PackGeom g = pack_geom(a.npol);
+  const uint64_t waves = ((uint64_t)a.nitems + g.ipw - 1u) / g.ipw;
+  const uint32_t wgrid = (uint32_t)((waves + 3u) / 4u);
+  const uint32_t nb = (uint32_t)(((uint64_t)a.nitems + kScanBlock - 1u) / kScanBlock);
+  hipLaunchKernelGGL(pack_codes_kernel, dim3(wgrid), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(pack_sums_kernel, dim3(nb), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(256), 0, s, a, nb);
+  hipLaunchKernelGGL(pack_bases_kernel, dim3(nb), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(pack_scatter_kernel, dim3(wgrid), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_overflow(const EvalArgs& a, const TileArgs* d_t, const uint32_t* d_overflow, uint32_t n_overflow,
                            hipStream_t s) {
   if (n_overflow == 0 || a.nrows == 0) return hipSuccess;

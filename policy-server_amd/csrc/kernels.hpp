@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "kwdev.hpp"
+#include "packed.hpp"
 #include "slots.hpp"
 
 namespace kw {
@@ -361,6 +362,29 @@ struct ScatterArgs {
   ScatterSeg seg[kMaxScatterSegs];
 };
 hipError_t launch_scatter(const ScatterArgs& a, hipStream_t s);
+
+// Bulk path, packed output (kw_validate_host_packed; the format and its arithmetic: packed.hpp): a
+// chunk's verdict words into bit-planes, absolute per-row exception offsets and the exception words,
+// behind the chunk's kernels on the same stream. Five launches, none waiting on another workgroup:
+//   codes    a lane per column, a wave per item (row, 64-column group) or per 64 / npol rows where
+//            npol <= 32: two ballots give the planes, the popcount of their AND the item's count
+//   sums     per-workgroup sums of the counts        scan   one workgroup over the sums, seeded with
+//   bases    the counts into absolute bases, exc_off        tot[0] (the chunks before); tot[1] = total
+//   scatter  each escaped lane's word at its item's base + its rank in the item, less tot[0]
+// All pointers at the chunk's first row / item; rows x G = nitems.
+struct PackArgs {
+  const uint32_t* words;  // [rows][npol]
+  const uint32_t* dict;   // [npol][3]
+  uint64_t* planes;       // [nitems][2]
+  uint32_t* ibase;        // [nitems]: counts, then absolute bases
+  uint32_t* exc_off;      // [rows], and [rows] = the total after the chunk
+  uint32_t* bsum;         // [ceil(nitems / kScanBlock)]
+  uint32_t* tot;          // [2]: the total before the chunk (read), after it (written)
+  uint32_t* exc;          // the chunk's exception words
+  uint32_t exc_cap;
+  uint32_t npol, G, nitems;
+};
+hipError_t launch_pack(const PackArgs& a, hipStream_t s);
 
 hipError_t launch_nfa_classify(const EvalArgs& a, const TileArgs* d_t, const NfaPass& np, uint32_t threads, hipStream_t s);
 // threads of the NFA pass's grid for `items` entities within a scratch budget

@@ -302,6 +302,95 @@ class PinnedWords:
         self.array = None
 
 
+class PackedVerdicts:
+    """The packed verdict form of a pass of rows x npol (kw_packed, include/kwgpu.h): `.planes`
+    uint64 [rows][G][2] bit-planes of a 2-bit code per column, `.dict` uint32 [npol][3] the words the
+    codes 0-2 stand for, `.exc_off` uint32 [rows + 1] and `.exc` the words of code 3 in (row, column)
+    order; `.exc_count` of them after a pass. word(row, col) and unpack() give the full words back.
+
+    exc_cap: capacity of `.exc` in words (default: a quarter of rows x npol, at least 1024;
+    Batch.validate_host_packed regrows an array it made itself). pinned=True takes the three output
+    arrays from page-locked memory (PinnedWords' allocator: direct DMA), which lives as long as any
+    view of them."""
+
+    def __init__(self, rows, npol, exc_cap=None, pinned=False, device=0):
+        import numpy as np
+        self.rows, self.npol = int(rows), int(npol)
+        self.G = (self.npol + 63) // 64
+        self.pinned, self.device = pinned, device
+        self.dict = np.zeros((self.npol, 3), dtype=np.uint32)
+        self.planes = self._alloc(self.rows * self.G * 2, np.uint64).reshape(self.rows, self.G, 2)
+        self.exc_off = self._alloc(self.rows + 1, np.uint32)
+        self.exc_count = 0
+        self._grow(max(1024, self.rows * self.npol // 4) if exc_cap is None else int(exc_cap))
+
+    @classmethod
+    def page_locked(cls, rows, npol, exc_cap=None, device=0):
+        """The output arrays in page-locked memory (kw_host_alloc), beside PinnedWords."""
+        return cls(rows, npol, exc_cap=exc_cap, pinned=True, device=device)
+
+    def _alloc(self, count, dtype):
+        import numpy as np
+        if not self.pinned:
+            return np.zeros(count, dtype=dtype)
+        words = count * np.dtype(dtype).itemsize // 4
+        return PinnedWords(words, self.device).array.view(dtype)[:count]
+
+    def _grow(self, cap):
+        import numpy as np
+        self.exc = self._alloc(max(cap, 1), np.uint32)[:cap]
+
+    def _struct(self):
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        return N.KwPacked(self.rows, self.npol, self.planes.ctypes.data_as(u64p), self.exc_off.ctypes.data_as(u32p),
+                          self.exc.ctypes.data_as(u32p), self.exc.size, self.dict.ctypes.data_as(u32p), self.exc_count)
+
+    @classmethod
+    def from_words(cls, env, policies, words, origin=VALIDATE, exc_cap=None):
+        """Diagnostic (kw_debug_pack_words): full words [rows][npol] packed on the host by the
+        reference encoder, under the dictionary a device pass over these policies uses. On
+        KW_E_NOSPACE raises NoSpace with the need in .need."""
+        import numpy as np
+        npol = len(policies)
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        rows = words.size // npol
+        self = cls(rows, npol, exc_cap=rows * npol if exc_cap is None else exc_cap)
+        arr = (C.c_int32 * npol)(*[env._idx(p) for p in policies])
+        st = self._struct()
+        rc = N.lib().kw_debug_pack_words(env._h, arr, npol, origin, words.ctypes.data_as(C.POINTER(C.c_uint32)), rows,
+                                         C.byref(st))
+        self.exc_count = st.exc_count
+        if rc == N.KW_E_NOSPACE:
+            raise NoSpace(st.exc_count)
+        raise_for(rc, "kw_debug_pack_words failed")
+        return self
+
+    def word(self, row, col):
+        """The verdict word of (row, col) (kw_packed_word)."""
+        w = C.c_uint32()
+        st = self._struct()
+        raise_for(N.lib().kw_packed_word(C.byref(st), row, col, C.byref(w)), "kw_packed_word: outside the pass")
+        return w.value
+
+    def unpack(self, row0=0, row1=None):
+        """Rows [row0, row1) as full words, flat [rows][npol] (kw_packed_unpack)."""
+        import numpy as np
+        row1 = self.rows if row1 is None else row1
+        out = np.empty(max(row1 - row0, 0) * self.npol, dtype=np.uint32)
+        st = self._struct()
+        raise_for(N.lib().kw_packed_unpack(C.byref(st), row0, row1, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                  "kw_packed_unpack failed")
+        return out
+
+
+class NoSpace(Exception):
+    """KW_E_NOSPACE of a packed pass: the exception words exceed the capacity; .need holds them."""
+
+    def __init__(self, need):
+        super().__init__(f"packed verdicts need {need} exception words")
+        self.need = int(need)
+
+
 class Batch:
     """A micro-batch of requests in SoA form (kw_batch)."""
 
@@ -406,6 +495,32 @@ class Batch:
         self.device = device
         self._npol = npol
         return out[:count]
+
+    def validate_host_packed(self, env, policies, out=None, origin=VALIDATE, device=0, chunk_rows=0):
+        """The bulk pass with the verdicts in the packed form (kw_validate_host_packed): returns a
+        PackedVerdicts. `out`: a reused one (page-locked: direct DMA); when its exception capacity is
+        too small the call raises NoSpace with the need. Without `out` the exception array is regrown
+        to the reported need and the pass run once more."""
+        npol = len(policies)
+        own = out is None
+        if own:
+            out = PackedVerdicts(self.n, npol)
+        elif out.rows != self.n or out.npol != npol:
+            raise ValueError("out must be a PackedVerdicts of this batch's rows and these policies")
+        arr = (C.c_int32 * npol)(*[env._idx(p) for p in policies])
+        for attempt in (0, 1):
+            st = out._struct()
+            rc = self._L.kw_validate_host_packed(env._h, self._h, arr, npol, origin, device, C.byref(st), chunk_rows)
+            out.exc_count = st.exc_count
+            if rc != N.KW_E_NOSPACE:
+                break
+            if not own or attempt:
+                raise NoSpace(st.exc_count)
+            out._grow(st.exc_count)
+        raise_for(rc, "kw_validate_host_packed failed")
+        self.device = device
+        self._npol = npol
+        return out
 
     def debug_plan(self, env, policies, origin=VALIDATE):
         """Diagnostic (kw_debug_plan): the tile kernel's plan for an all-pairs pass, on the host."""

@@ -79,6 +79,13 @@ class KwTiming(C.Structure):
                 ("classify_bytes", C.c_double), ("evaluate_bytes", C.c_double)]
 
 
+class KwPacked(C.Structure):
+    """kw_packed: the packed verdict form (include/kwgpu.h)."""
+    _fields_ = [("rows", C.c_uint64), ("npol", C.c_uint32), ("planes", C.POINTER(C.c_uint64)),
+                ("exc_off", C.POINTER(C.c_uint32)), ("exc", C.POINTER(C.c_uint32)), ("exc_cap", C.c_size_t),
+                ("dict", C.POINTER(C.c_uint32)), ("exc_count", C.c_size_t)]
+
+
 EXPORTS = [
     "kw_env_build", "kw_env_build_yaml", "kw_yaml_to_json", "kw_env_serialize", "kw_env_deserialize", "kw_env_destroy", "kw_env_lookup",
     "kw_env_policy_count", "kw_env_policy_id", "kw_env_is_group", "kw_env_get_policy_mode",
@@ -88,7 +95,8 @@ EXPORTS = [
     "kw_env_pattern", "kw_env_classify", "kw_batch_wide_arg", "kw_batch_group_causes", "kw_debug_plan", "kw_debug_copy_jobs", "kw_debug_reorder",
     "kw_debug_tile_descs", "kw_debug_tile_cost", "kw_debug_tile_slot",
     "kw_batch_from_json", "kw_batch_from_soa", "kw_batch_view", "kw_batch_to_device", "kw_batch_to_device_async",
-    "kw_stream_create", "kw_stream_destroy", "kw_validate_host", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
+    "kw_stream_create", "kw_stream_destroy", "kw_validate_host", "kw_validate_host_packed", "kw_packed_word",
+    "kw_packed_unpack", "kw_debug_pack_words", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
     "kw_batch_destroy", "kw_debug_host_walk", "kw_validate_batch", "kw_validate_rows", "kw_batch_verdicts",
     "kw_validate_timed", "kw_format_response", "kw_format_response_doc", "kw_env_group_members", "kw_evaluate",
     "kw_service_constraints", "kw_metrics_create", "kw_metrics_destroy", "kw_metrics_record", "kw_metrics_render",
@@ -158,6 +166,10 @@ def lib():
         "kw_validate_rows": (ip, [vp, vp, C.POINTER(i32), ip, vp]),
         "kw_batch_verdicts": (ip, [vp, C.POINTER(u32), sz]),
         "kw_validate_host": (ip, [vp, vp, C.POINTER(i32), u32, ip, ip, C.POINTER(u32), sz, u32]),
+        "kw_validate_host_packed": (ip, [vp, vp, C.POINTER(i32), u32, ip, ip, C.POINTER(KwPacked), u32]),
+        "kw_packed_word": (ip, [C.POINTER(KwPacked), u64, u32, C.POINTER(u32)]),
+        "kw_packed_unpack": (ip, [C.POINTER(KwPacked), u64, u64, C.POINTER(u32)]),
+        "kw_debug_pack_words": (ip, [vp, C.POINTER(i32), u32, ip, C.POINTER(u32), u64, C.POINTER(KwPacked)]),
         "kw_batch_pin_host": (ip, [vp, ip]),
         "kw_host_alloc": (ip, [ip, sz, C.POINTER(vp)]),
         "kw_host_free": (None, [vp]),
