@@ -384,6 +384,70 @@ int kw_packed_unpack(const kw_packed *p, uint64_t row0, uint64_t row1, uint32_t 
  * for kw_validate_host_packed (rows from the caller); KW_E_NOSPACE likewise. */
 int kw_debug_pack_words(const kw_env *env, const int32_t *policies, uint32_t npol, int origin, const uint32_t *words,
                         uint64_t rows, kw_packed *out);
+/* The summary form of a pass of rows x npol: lossy and fixed-size, for callers that count before
+ * they read (an audit scan, a metrics exporter). Reduced on the device, so only the counters and, if
+ * asked, two bits per pair cross PCIe instead of every word. With G = ceil(npol / 64) as in kw_packed,
+ * all arrays caller-owned:
+ *   col      u64[npol][KW_SUM_N]: col[c][k] counts column c's words. k 0-4: the words with the named
+ *            bit set; 5-7: by F_STATUS value; KW_SUM_REASON + r: the words whose KW_REASON is r <= 15
+ *            (index 16: no violation); KW_SUM_REASON_OTHER: any other reason. No product word has
+ *            one; the KW_POISON_VERDICTS sentinel does, so a tile that was never evaluated shows up
+ *            there. Indices 9-15 are zero.
+ *   planes   u64[rows][G][2], or NULL for the counters alone: bit c of planes[r][g][0] is set when
+ *            the word of column 64 g + c lacks KW_F_ALLOWED (the final answer is a reject), bit c of
+ *            planes[r][g][1] when its KW_REASON is non-zero (the policy found something, whatever
+ *            mode, bypass or constraints made of it): the pairs worth a message. A word counted
+ *            in KW_SUM_REASON_OTHER sets both bits whatever its other bits say. Bits of columns
+ *            >= npol are 0.
+ * The same input gives the same bytes. The V_ALLOWED / V_MUTATED / INIT_ERROR counters are the
+ * accepted / mutated / error counts kubewarden_policy_evaluations_total carries per policy
+ * (src/metrics.rs:49-140) without the per-request attributes: the attribute sets with resource kind,
+ * operation and namespace still need kw_metrics_record over the words. */
+enum {
+  KW_SUM_F_ALLOWED = 0,
+  KW_SUM_V_ALLOWED = 1,
+  KW_SUM_V_MUTATED = 2,
+  KW_SUM_F_PATCH = 3,
+  KW_SUM_BYPASS = 4,
+  KW_SUM_FST_VANILLA = 5,
+  KW_SUM_FST_MUTATION_REFUSED = 6,
+  KW_SUM_FST_INIT_ERROR = 7,
+  KW_SUM_REASON_OTHER = 8, /* 9..15: zero */
+  KW_SUM_REASON = 16,      /* + kw_reason, 0..15 */
+  KW_SUM_N = 32
+};
+typedef struct kw_summary {
+  uint64_t rows;
+  uint32_t npol;
+  uint64_t *col;    /* u64[npol][KW_SUM_N] */
+  uint64_t *planes; /* u64[rows][G][2], or NULL: counters only */
+} kw_summary;
+/* The summary of the batch's last device pass (kw_validate_batch, kw_validate_rows or a bulk pass),
+ * reduced in place on the device; synchronises with the pass's stream as kw_batch_verdicts does and
+ * reads back only col and, if asked, the planes (in batch-row order). out->rows / npol must equal the
+ * pass's, else KW_E_ARG (so is a batch without a pass); a kw_validate_rows pass is one column. */
+int kw_batch_summary(kw_batch *b, kw_summary *out);
+/* kw_validate_host with the summary as its only output: each chunk is reduced on the device behind
+ * its kernels, its planes go out while the next chunk runs (direct DMA into page-locked planes, else
+ * through pinned bounce blocks), the totals after the last chunk. out->rows = the batch's, npol = the
+ * list's, else KW_E_ARG. The verdict words stay on the device: kw_batch_verdict_rows,
+ * kw_batch_verdicts and kw_batch_summary work on the pass afterwards. */
+int kw_validate_host_summary(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
+                             int device, kw_summary *out, uint32_t chunk_rows);
+/* The full words of n chosen batch rows of the last pass, out[n][row_words] (row_words: npol, or 1
+ * after kw_validate_rows), gathered on the device and read back in one copy; any order, repeats
+ * allowed. Loads the pass's side data as kw_batch_verdicts does, so kw_batch_wide_arg,
+ * kw_batch_group_causes and the formatters work on the fetched words. A row >= the pass's rows gives
+ * KW_E_ARG; n = 0 is KW_OK. The audit flow: summary, the rows whose plane 1 is non-zero, their words,
+ * messages. */
+int kw_batch_verdict_rows(kw_batch *b, const uint64_t *rows, size_t n, uint32_t *out);
+/* The shape of the batch's last device pass, as kw_batch_summary and kw_batch_verdict_rows see it:
+ * its rows and its verdict words per row (npol, or 1 after kw_validate_rows). A caller sizes the
+ * output of kw_batch_verdict_rows by it. KW_E_ARG for a batch without a pass. */
+int kw_batch_last_pass(const kw_batch *b, uint64_t *rows, uint32_t *row_words);
+/* Diagnostic (tests, documents): full words [rows][npol] into the summary form on the host, by the
+ * reference reducer. */
+int kw_debug_summarize_words(const uint32_t *words, uint64_t rows, uint32_t npol, kw_summary *out);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes

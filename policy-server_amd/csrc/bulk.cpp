@@ -46,6 +46,23 @@
 // and after the last chunk out(K-1), the last two exception blocks' copy-out, then the same drain. A
 // pass that runs unchunked packs its verdict buffer after the pass in row slabs by the same steps.
 // (out(k-2) for page-locked outputs was tried: the pass was no shorter, profiles/r09_bulk_packed.txt.)
+//
+// The summary output form (kw_validate_host_summary, summary.hpp) replaces read_back and copy_out
+// too; it needs no event beyond the three per chunk. The running u64 totals are zeroed on sc ahead of
+// the first chunk. Per chunk, after launch / overflow:
+//   summarize      sc: the summary kernel over the chunk's rows of the verdict buffer (planes into
+//                  the device plane array at the chunk's rows; none without planes), then the totals
+//                  kernel, which adds the chunk's partial blocks into the running totals: ordered by
+//                  sc, so chunk k + 1's partial blocks overwrite chunk k's only after they were added
+//   read_back      sc: records ev[3k+1]; s_out: waits ev[3k+1], D2H of the chunk's planes into the
+//                  caller's page-locked array or bounce block k & 1 (no copy without planes), records
+//                  ev[3k+2]
+//   out(k-1)       (pageable planes) host waits ev[3(k-1)+2], copies bounce block (k-1) & 1 out
+// and after the last chunk out(K-1), then on s_out (which has waited for ev[3(K-1)+1], recorded behind
+// the last totals kernel) the D2H of the totals into a pinned block, a host wait for s_out, the copy
+// into the caller's col, and the same drain. The verdict buffer keeps every chunk's words, so
+// kw_batch_verdict_rows and kw_batch_verdicts work on the pass. A pass that runs unchunked is
+// summarised after the pass in row slabs by the same steps.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -57,6 +74,7 @@
 #include "packed.hpp"
 #include "pass.hpp"
 #include "plan.hpp"
+#include "summary.hpp"
 #include "upload.hpp"
 
 namespace kw {
@@ -89,6 +107,7 @@ struct Res {
   BlockLease bounce[2];     // pageable output: verdicts land here
   // packed output: the device arrays (dictionary, totals, scan sums, planes, offsets, item bases),
   // the exception ring, the pinned totals and dictionary, the pageable output's exception blocks
+  // summary output: dfix holds the device planes, totals and partial blocks, hfix the pinned totals
   BlockLease dfix, dexc, hfix, xb[3];
   StreamLease s_out, s_in;
   EventLease ev;
@@ -161,6 +180,11 @@ struct BulkPass {
   size_t slot_words = 0, off_at = 0;  // off_at: the offsets' place in a bounce block
   std::vector<char> xissued;
   bool nospace = false;
+  // summary output (kw_validate_host_summary): sm set, `out` null; rb, G and d_planes as above; the
+  // running totals [npol][KW_SUM_N] and the workgroups' partial blocks (Res::dfix)
+  kw_summary* sm = nullptr;
+  uint64_t* d_stot = nullptr;
+  uint32_t* d_spart = nullptr;
 
   BulkPass(const kw_env* e, kw_batch* b, const int32_t* p, uint32_t np, int o, int dev, uint32_t* w, size_t c, uint32_t cr)
       : env(e), kb(b), policies(p), npol(np), origin(o), device(dev), out(w), count(c), chunk_rows(cr) {}
@@ -205,12 +229,7 @@ struct BulkPass {
     // the others through the pinned staging, filled by the host workers
     dma.assign(pieces.size(), 0);
     if (!kb->host_pinned.empty())
-      for (size_t i = 0; i < pieces.size(); ++i) {
-        hipPointerAttribute_t pa;
-        dma[i] = pieces[i].bytes && hipPointerGetAttributes(&pa, pieces[i].src) == hipSuccess &&
-                 pa.type == hipMemoryTypeHost;
-        (void)hipGetLastError();
-      }
+      for (size_t i = 0; i < pieces.size(); ++i) dma[i] = pieces[i].bytes && page_locked(pieces[i].src);
     sc = D.stream;
     // (NFA elements: their pre-pass reads whole columns, so such passes are not chunked)
     chunked = pl.tiles.size() == 1 && pl.wide.groups.empty() && pl.nwide == 0 && !pl.rows_mode &&
@@ -226,8 +245,8 @@ struct BulkPass {
     return KW_OK;
   }
 
-  // One upload, the full pass, one read-back.
-  int run_unchunked() {
+  // One upload, the full pass.
+  int run_whole() {
     DeviceBatch& D = *kb->dev;
     std::vector<CopySeg> segs;
     for (size_t i = 0; i < pieces.size(); ++i)
@@ -238,7 +257,12 @@ struct BulkPass {
     for (size_t i = 0; i < pieces.size(); ++i)
       if (pieces[i].bytes && dma[i])
         HIPCHK(hipMemcpyAsync(D.cols + pieces[i].at, pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice, sc));
-    if (int rc = run_validate(env, kb, pl, origin, false, sc)) return rc;
+    return run_validate(env, kb, pl, origin, false, sc);
+  }
+
+  // One upload, the full pass, one read-back.
+  int run_unchunked() {
+    if (int rc = run_whole()) return rc;
     return read_verdicts(kb, out, count);
   }
 
@@ -276,10 +300,10 @@ struct BulkPass {
     const uint64_t tper = chunk_tiles(ntiles, G.rows, per);
     tb = chunk_bounds(ntiles, G.rows, per, ramp);
     K = tb.size() - 1;
-    hipPointerAttribute_t attr;
     const bool direct = Knobs::on<KW_BULK_DIRECT>();  // A/B knob
-    pinned = direct && (pk ? packed_pinned() : hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeHost);
-    (void)hipGetLastError();  // a pageable pointer leaves an error state behind
+    pinned = direct && (pk   ? packed_pinned()
+                        : sm ? summary_pinned()
+                             : page_locked(out));
     const int depth_knob = Knobs::num<KW_BULK_DEPTH>();  // A/B knob, 0 = unbounded
     depth = bulk_depth(depth_knob, std::count(dma.begin(), dma.end(), 1) > 0);
     // (the largest chunk: `per` grows past ~240 chunks)
@@ -287,11 +311,15 @@ struct BulkPass {
     for (uint64_t k = 0; k < K; ++k) max_rows = std::max(max_rows, row_of(tb[k + 1]) - row_of(tb[k]));
     dcap = tper + tper / 4 + 64;
     res.emplace(sc);
-    if (!pinned && !pk)
+    if (!pinned && !pk && !sm)
       for (BlockLease& b : res->bounce) HIPCHK(b.alloc(host_pool(), device, (size_t)max_rows * npol * 4));
     if (pk) {
       for (uint64_t k = 0; k <= K; ++k) rb.push_back(row_of(tb[k]));
       if (int rc = setup_packed(max_rows)) return rc;
+    }
+    if (sm) {
+      for (uint64_t k = 0; k <= K; ++k) rb.push_back(row_of(tb[k]));
+      if (int rc = setup_summary(max_rows)) return rc;
     }
     if (int rc = alloc_descs()) return rc;
     // (the scatter kernel's argument holds kMaxScatterSegs ranges: a layout with more staged pieces
@@ -318,13 +346,7 @@ struct BulkPass {
 
   // Direct DMA only when all three output arrays are page-locked.
   bool packed_pinned() const {
-    for (const void* p : {(const void*)pk->planes, (const void*)pk->exc_off, (const void*)pk->exc}) {
-      hipPointerAttribute_t a;
-      const bool host = p && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
-      (void)hipGetLastError();
-      if (!host) return false;
-    }
-    return true;
+    return page_locked(pk->planes) && page_locked(pk->exc_off) && page_locked(pk->exc);
   }
 
   // The packed form's blocks for chunks of at most max_rows rows (rb, K and `pinned` are set), the
@@ -460,17 +482,7 @@ struct BulkPass {
   // A pass that ran unchunked (run_unchunked's upload and pass): its verdict buffer packed in row
   // slabs through the chunked form's steps.
   int run_unchunked_packed() {
-    DeviceBatch& D = *kb->dev;
-    std::vector<CopySeg> segs;
-    for (size_t i = 0; i < pieces.size(); ++i)
-      if (pieces[i].bytes && !dma[i]) segs.push_back({st + pieces[i].at, pieces[i].src, pieces[i].bytes});
-    parallel_copy_segs(segs);
-    for (const CopySeg& c : segs)
-      HIPCHK(hipMemcpyAsync(D.cols + ((uint8_t*)c.dst - st), c.dst, c.bytes, hipMemcpyHostToDevice, sc));
-    for (size_t i = 0; i < pieces.size(); ++i)
-      if (pieces[i].bytes && dma[i])
-        HIPCHK(hipMemcpyAsync(D.cols + pieces[i].at, pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice, sc));
-    if (int rc = run_validate(env, kb, pl, origin, false, sc)) return rc;
+    if (int rc = run_whole()) return rc;
     const uint64_t rows = kb->b.n, per = chunk_rows ? chunk_rows : (uint64_t)Knobs::num<KW_BULK_CHUNK>();
     const uint64_t slab = std::max<uint64_t>({1, per, (rows + 239) / 240});
     for (uint64_t r = 0; r < rows; r += slab) rb.push_back(r);
@@ -496,6 +508,112 @@ struct BulkPass {
     if (rc != KW_OK && rc != KW_E_NOSPACE) return rc;
     const int src = load_side_data(kb, sc);
     return src ? src : rc;
+  }
+
+  // ---- summary output ----
+
+  // Direct DMA when the planes are page-locked (without planes nothing but the totals goes out).
+  bool summary_pinned() const { return !sm->planes || page_locked(sm->planes); }
+
+  // The summary form's blocks for chunks of at most max_rows rows (rb, K and `pinned` are set) and
+  // the running totals zeroed on sc ahead of the first summary kernel.
+  int setup_summary(uint64_t max_rows) {
+    const uint64_t rows = kb->b.n;
+    G = packed_groups(npol);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_tot = up(summary_col_words(npol) * 8), b_part = up(summary_part_bytes(max_rows, npol));
+    const size_t b_planes = sm->planes ? up((size_t)rows * G * 16) : 0;
+    HIPCHK(res->dfix.alloc(dev_pool(), device, b_planes + b_tot + b_part));
+    uint8_t* d = (uint8_t*)res->dfix.p;
+    d_planes = (uint64_t*)d, d += b_planes;
+    d_stot = (uint64_t*)d, d += b_tot;
+    d_spart = (uint32_t*)d;
+    HIPCHK(res->hfix.alloc(host_pool(), device, b_tot));
+    if (!pinned && sm->planes)
+      for (BlockLease& b : res->bounce) HIPCHK(b.alloc(host_pool(), device, std::max<size_t>((size_t)max_rows * G * 16, 16)));
+    HIPCHK(hipMemsetAsync(d_stot, 0, summary_col_words(npol) * 8, sc));
+    return KW_OK;
+  }
+
+  // The chunk's words reduced on the device behind its kernels, into the running totals.
+  int summarize(uint64_t k) {
+    DeviceBatch& D = *kb->dev;
+    const uint64_t r0 = rb[k], r1 = rb[k + 1];
+    SumArgs a;
+    a.words = D.verdicts + r0 * npol;
+    a.planes = sm->planes ? d_planes + 2 * r0 * G : nullptr;
+    a.part = d_spart;
+    a.tot = d_stot;
+    a.rows = r1 - r0;
+    a.npol = npol;
+    HIPCHK(launch_summary(a, sc));
+    return KW_OK;
+  }
+
+  // The chunk's planes to the host behind its summary kernels.
+  int read_back_summary(uint64_t k) {
+    const EventLease& ev = res->ev;
+    hipStream_t s_out = res->s_out.s;
+    const uint64_t r0 = rb[k], r1 = rb[k + 1];
+    HIPCHK(hipEventRecord(ev[3 * k + 1], sc));
+    HIPCHK(hipStreamWaitEvent(s_out, ev[3 * k + 1], 0));
+    if (sm->planes && r1 > r0)
+      HIPCHK(hipMemcpyAsync(pinned ? (void*)(sm->planes + 2 * r0 * G) : res->bounce[k & 1].p, d_planes + 2 * r0 * G,
+                            (size_t)(r1 - r0) * G * 16, hipMemcpyDeviceToHost, s_out));
+    HIPCHK(hipEventRecord(ev[3 * k + 2], s_out));
+    return KW_OK;
+  }
+
+  // Pageable planes: the chunk's from its bounce block to the caller's array.
+  int out_summary(uint64_t k) {
+    if (pinned || !sm->planes) return KW_OK;  // (KW_BULK_DIRECT=0 clears `pinned` for a counters-only pass too)
+    const auto t0 = clk::now();
+    HIPCHK(hipEventSynchronize(res->ev[3 * k + 2]));
+    const uint64_t r0 = rb[k], r1 = rb[k + 1];
+    parallel_copy_segs({{sm->planes + 2 * r0 * G, res->bounce[k & 1].p, (size_t)(r1 - r0) * G * 16}});
+    t.out += since(t0);
+    return KW_OK;
+  }
+
+  // After the last chunk: its planes out, then the totals, read back once.
+  int end_summary() {
+    if (K)
+      if (int rc = out_summary(K - 1)) return rc;
+    const size_t b_tot = summary_col_words(npol) * 8;
+    hipStream_t s_out = res->s_out.s;  // (has waited for the last chunk's ev[3k+1], behind its totals kernel)
+    HIPCHK(hipMemcpyAsync(res->hfix.p, d_stot, b_tot, hipMemcpyDeviceToHost, s_out));
+    HIPCHK(hipStreamSynchronize(s_out));
+    memcpy(sm->col, res->hfix.p, b_tot);
+    return KW_OK;
+  }
+
+  // A pass that ran unchunked: its verdict buffer summarised in row slabs through the chunked form's
+  // steps.
+  int run_unchunked_summary() {
+    if (int rc = run_whole()) return rc;
+    const uint64_t rows = kb->b.n, per = chunk_rows ? chunk_rows : (uint64_t)Knobs::num<KW_BULK_CHUNK>();
+    const uint64_t slab = std::max<uint64_t>({1, per, (rows + 239) / 240});
+    for (uint64_t r = 0; r < rows; r += slab) rb.push_back(r);
+    rb.push_back(rows);
+    K = rb.size() - 1;
+    if (K == 0) {
+      memset(sm->col, 0, summary_col_words(npol) * 8);
+      return load_side_data(kb, sc);
+    }
+    pinned = Knobs::on<KW_BULK_DIRECT>() && summary_pinned();
+    res.emplace(sc);
+    int rc = setup_summary(std::min(slab, rows));
+    if (rc == KW_OK) rc = res->s_out.get(device) == hipSuccess && res->ev.get(device, 3 * K) == hipSuccess ? KW_OK : KW_E_DEVICE;
+    for (uint64_t k = 0; k < K && rc == KW_OK; ++k) {
+      rc = summarize(k);
+      if (rc == KW_OK) rc = read_back_summary(k);
+      if (rc == KW_OK && k >= 1) rc = out_summary(k - 1);
+    }
+    if (rc == KW_OK) rc = end_summary();
+    res->drain();
+    res.reset();
+    if (rc != KW_OK) return rc;
+    return load_side_data(kb, sc);
   }
 
   // The chunk's columns: their H2D starts at once, and the descriptor build after it then reads
@@ -645,12 +763,16 @@ struct BulkPass {
     if (pk) {
       if (int rc = pack(k)) return rc;
       if (int rc = read_back_packed(k)) return rc;
+    } else if (sm) {
+      if (int rc = summarize(k)) return rc;
+      if (int rc = read_back_summary(k)) return rc;
     } else if (int rc = read_back(k)) {
       return rc;
     }
     t.enq += since(t2);
     if (k == 0) t.first = since(t_start);
     if (pk) return k >= 1 ? out_packed(k - 1) : KW_OK;
+    if (sm) return k >= 1 ? out_summary(k - 1) : KW_OK;
     return k >= 1 ? copy_out(k - 1) : KW_OK;  // (bounce[k & 1] was last read by chunk k - 2's copy-out)
   }
 
@@ -718,6 +840,22 @@ int validate_host_packed(const kw_env* env, kw_batch* kb, const int32_t* policie
   int rc = P.setup();
   for (uint64_t k = 0; k < P.K && rc == KW_OK; ++k) rc = P.chunk(k);
   if (rc == KW_OK) rc = P.end_packed();
+  return P.finish(rc);
+}
+
+int validate_host_summary(const kw_env* env, kw_batch* kb, const int32_t* policies, uint32_t npol, int origin, int device,
+                          kw_summary* out, uint32_t chunk_rows) {
+  if (!env || !kb || !out || !policies || npol == 0 || !out->col) return KW_E_ARG;
+  if (env->e.device < 0 || !env->e.d_blob) return KW_E_DEVICE;
+  if (device != env->e.device || out->rows != kb->b.n || out->npol != npol) return KW_E_ARG;
+  BulkPass P(env, kb, policies, npol, origin, device, nullptr, (size_t)out->rows * npol, chunk_rows);
+  P.sm = out;
+  if (int rc = P.plan()) return rc;
+  if (!P.chunked) return P.run_unchunked_summary();
+  if (int rc = P.prepare()) return rc;
+  int rc = P.setup();
+  for (uint64_t k = 0; k < P.K && rc == KW_OK; ++k) rc = P.chunk(k);
+  if (rc == KW_OK) rc = P.end_summary();
   return P.finish(rc);
 }
 

@@ -126,6 +126,7 @@ struct DeviceBatch {
   // region's rows (0: not split); dev_b: the reordered batch the planner reads (its offsets only:
   // the string bytes are dropped after the upload).
   std::vector<uint64_t> perm;
+  std::vector<uint64_t> inv_perm;  // the device row of each batch row (kw_batch_verdict_rows builds it once)
   uint64_t split = 0;
   std::unique_ptr<Batch> dev_b;
   // the last all-pairs pass's plan (pass.cpp validate_cached): reused while the

@@ -1984,6 +1984,167 @@ hipError_t launch_pack(const PackArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- summary form (kernels.hpp SumArgs, summary.hpp) --------------------------------------------
+
+#ifndef KW_SUM_LDS  // the 17 reason buckets: 1 a per-wave LDS table, 0 compare-and-add in registers (build-time A/B)
+#define KW_SUM_LDS 1
+#endif
+constexpr uint32_t kSumBuckets = 17;  // reasons 0..15 and "other"; odd, so also the LDS table's row stride
+
+__global__ void __launch_bounds__(256) summary_kernel(SumArgs a, SumGeom g) {
+  __shared__ uint32_t wg[64 * KW_SUM_N];  // the workgroup's partial block
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, grp = blockIdx.y;
+  for (uint32_t i = threadIdx.x; i < 64u * KW_SUM_N; i += 256u) wg[i] = 0;
+#if KW_SUM_LDS
+  __shared__ uint32_t rs[kSumWaves * 64 * kSumBuckets];
+  uint32_t* mine = rs + (wave * 64u + lane) * kSumBuckets;
+  for (uint32_t b = 0; b < kSumBuckets; ++b) mine[b] = 0;
+#else
+  uint32_t mine[kSumBuckets];
+#pragma unroll
+  for (uint32_t b = 0; b < kSumBuckets; ++b) mine[b] = 0;
+#endif
+  __syncthreads();
+  const uint32_t w = g.p.w, ipi = g.p.ipi, T = g.p.T;
+  const uint32_t sub = lane / w, c = lane % w, col = 64u * grp + c;
+  const bool lane_on = sub < ipi && col < a.npol;  // (sum_lane's column part: fixed for the kernel)
+  const uint64_t mask = w == 64u ? ~0ull : (1ull << w) - 1ull;
+  const uint64_t nwaves = (uint64_t)kSumWaves * gridDim.x;
+  const bool planes = a.planes != nullptr;
+  uint32_t n_fa = 0, n_va = 0, n_vm = 0, n_fp = 0, n_by = 0, n_s1 = 0, n_s2 = 0, n_s3 = 0;
+  for (uint64_t unit = (uint64_t)blockIdx.x * kSumWaves + wave; unit < g.units; unit += nwaves) {  // wave-uniform
+    const uint64_t row0 = unit * g.p.ipw;
+    // the unit's words first: up to kSumRounds loads in flight per lane
+    uint32_t x[kSumRounds], onm = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < kSumRounds; ++t) {
+      const SumLane L = sum_lane(g, a.rows, a.npol, grp, unit, t, lane);
+      x[t] = L.on ? __builtin_nontemporal_load(a.words + L.row * a.npol + L.col) : 0u;
+      onm |= (L.on ? 1u : 0u) << t;
+    }
+    uint64_t my_lo = 0, my_hi = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < kSumRounds; ++t) {
+      if (t >= T) continue;  // wave-uniform (not a break: the loop unrolls fully, x[t] stays a register)
+      const uint32_t v = x[t];
+      const bool on = (onm >> t) & 1u;
+      // (a lane that holds no word has v = 0: no flag, status None)
+      n_fa += (v >> 2) & 1u;
+      n_va += v & 1u;
+      n_vm += (v >> 1) & 1u;
+      n_fp += (v >> 6) & 1u;
+      n_by += (v >> 5) & 1u;
+      const uint32_t st = (v & KW_F_STATUS_MASK) >> KW_F_STATUS_SHIFT;
+      n_s1 += st == 1u ? 1u : 0u;
+      n_s2 += st == 2u ? 1u : 0u;
+      n_s3 += st == 3u ? 1u : 0u;
+      const uint32_t r = KW_REASON(v), b = r < kSumBuckets - 1u ? r : kSumBuckets - 1u;
+#if KW_SUM_LDS
+      if (on) __hip_atomic_fetch_add(mine + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#else
+#pragma unroll
+      for (uint32_t q = 0; q < kSumBuckets; ++q) mine[q] += on && b == q ? 1u : 0u;
+#endif
+      if (planes) {
+        const uint64_t blo = __ballot(on && sum_bit_reject(v)), bhi = __ballot(on && sum_bit_found(v));
+        const uint32_t j = lane - t * ipi;  // lane t * ipi + j keeps the round's row j
+        if (lane >= t * ipi && j < ipi) {
+          my_lo = (blo >> (j * w)) & mask;
+          my_hi = (bhi >> (j * w)) & mask;
+        }
+      }
+    }
+    if (planes && lane < g.p.ipw && row0 + lane < a.rows)
+      *(ulonglong2*)(a.planes + 2u * ((row0 + lane) * g.G + grp)) = make_ulonglong2(my_lo, my_hi);
+  }
+  // the waves of the workgroup, and the lanes that share a column, into the partial block
+  if (lane_on) {
+    uint32_t* d = wg + c * KW_SUM_N;
+    auto add = [d](uint32_t k, uint32_t n) {
+      if (n) __hip_atomic_fetch_add(d + k, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    add(KW_SUM_F_ALLOWED, n_fa), add(KW_SUM_V_ALLOWED, n_va), add(KW_SUM_V_MUTATED, n_vm), add(KW_SUM_F_PATCH, n_fp);
+    add(KW_SUM_BYPASS, n_by), add(KW_SUM_FST_VANILLA, n_s1), add(KW_SUM_FST_MUTATION_REFUSED, n_s2);
+    add(KW_SUM_FST_INIT_ERROR, n_s3);
+#pragma unroll
+    for (uint32_t b = 0; b + 1u < kSumBuckets; ++b) add(KW_SUM_REASON + b, mine[b]);
+    add(KW_SUM_REASON_OTHER, mine[kSumBuckets - 1u]);
+  }
+  __syncthreads();
+  uint32_t* out = a.part + ((uint64_t)grp * gridDim.x + blockIdx.x) * g.cols * KW_SUM_N;
+  for (uint32_t i = threadIdx.x; i < g.cols * KW_SUM_N; i += 256u) out[i] = wg[i];
+}
+
+// A workgroup per column: its 256 threads are kSumSlices slices of the column's KW_SUM_N counters,
+// slice q sums the partial blocks q, q + kSumSlices, ... (four loads in flight a thread), and one
+// thread per counter adds the slices in order into the running total. (One thread per counter over
+// all the blocks — 2048 threads on the whole device for 64 columns — took 105 us a launch, four times
+// the reduction itself: profiles/r10_summary.txt.)
+constexpr uint32_t kSumSlices = 256 / KW_SUM_N;
+__global__ void __launch_bounds__(256) summary_totals_kernel(SumArgs a, SumGeom g) {
+  __shared__ uint64_t sl[kSumSlices][KW_SUM_N];
+  const uint32_t col = blockIdx.x, k = threadIdx.x % KW_SUM_N, q = threadIdx.x / KW_SUM_N;
+  const uint32_t grp = col / 64u, c = col - 64u * grp;
+  const uint64_t stride = (uint64_t)g.cols * KW_SUM_N;
+  const uint32_t* p = a.part + (uint64_t)grp * g.grid_x * stride + c * KW_SUM_N + k;
+  uint64_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  uint32_t x = q;
+  for (; x + 3u * kSumSlices < g.grid_x; x += 4u * kSumSlices) {
+    s0 += p[x * stride];
+    s1 += p[(x + kSumSlices) * stride];
+    s2 += p[(x + 2u * kSumSlices) * stride];
+    s3 += p[(x + 3u * kSumSlices) * stride];
+  }
+  for (; x < g.grid_x; x += kSumSlices) s0 += p[x * stride];
+  sl[q][k] = s0 + s1 + s2 + s3;
+  __syncthreads();
+  if (q == 0) {
+    uint64_t s = 0;
+    for (uint32_t j = 0; j < kSumSlices; ++j) s += sl[j][k];
+    a.tot[col * (uint32_t)KW_SUM_N + k] += s;
+  }
+}
+
+namespace {
+uint32_t device_cus() {
+  thread_local int c_dev = -1, c_ncu = 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev != c_dev) {
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 0;
+    c_dev = dev;
+    c_ncu = ncu;
+  }
+  return (uint32_t)std::max(c_ncu, 0);
+}
+}  // namespace
+
+size_t summary_part_bytes(uint64_t rows, uint32_t npol) {
+  return (size_t)sum_part_words(sum_geom(rows, npol, device_cus())) * sizeof(uint32_t);
+}
+
+hipError_t launch_summary(const SumArgs& a, hipStream_t s) {
+  if (a.rows == 0 || a.npol == 0) return hipSuccess;
+  const SumGeom g = sum_geom(a.rows, a.npol, device_cus());
+  if (sum_wg_rows(g) >> 32) return hipErrorInvalidValue;  // (sum_geom keeps it below: tests/summary_check.cpp)
+  hipLaunchKernelGGL(summary_kernel, dim3(g.grid_x, g.G), dim3(256), 0, s, a, g);
+  hipLaunchKernelGGL(summary_totals_kernel, dim3(a.npol), dim3(256), 0, s, a, g);
+  return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) gather_rows_kernel(GatherArgs a) {
+  const uint64_t nw = a.n * a.row_words, nt = (uint64_t)gridDim.x * 256u;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nw; i += nt)
+    a.out[i] = a.words[a.rows[i / a.row_words] * a.row_words + i % a.row_words];
+}
+
+hipError_t launch_gather_rows(const GatherArgs& a, hipStream_t s) {
+  if (a.n == 0 || a.row_words == 0) return hipSuccess;
+  const uint64_t nw = a.n * a.row_words;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (nw + 255u) / 256u)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_overflow(const EvalArgs& a, const TileArgs* d_t, const uint32_t* d_overflow, uint32_t n_overflow,
                            hipStream_t s) {
   if (n_overflow == 0 || a.nrows == 0) return hipSuccess;

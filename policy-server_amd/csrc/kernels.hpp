@@ -7,6 +7,7 @@
 #include "kwdev.hpp"
 #include "packed.hpp"
 #include "slots.hpp"
+#include "summary.hpp"
 
 namespace kw {
 
@@ -385,6 +386,42 @@ struct PackArgs {
   uint32_t npol, G, nitems;
 };
 hipError_t launch_pack(const PackArgs& a, hipStream_t s);
+
+// The summary form (kw_batch_summary, kw_validate_host_summary; the form and the geometry:
+// summary.hpp): a streaming pass over row-major verdict words, each read once. Two launches:
+//   summary  a lane keeps one column for the whole kernel, a wave one column group (grid.y) and the
+//            units of rows its index strides to. The flag and status counters are plain adds in
+//            registers; the 17 reason buckets a per-wave LDS table [lane][bucket] of odd row stride
+//            (lanes with the same reason hit distinct banks; KW_SUM_LDS=0 builds the compare-and-add
+//            form in registers: profiles/r10_summary.txt has the two side by side). The planes come
+//            from two ballots a round, lane j keeping round j's, stored 16 bytes a row after a unit.
+//            The waves of a workgroup, and the lanes that share a column where npol <= 32, combine in
+//            LDS; the workgroup writes one u32 partial block [columns][KW_SUM_N]. No global atomics.
+//   totals   a workgroup per column sums the partial blocks in eight slices side by side, then one
+//            thread per counter adds the slices in a fixed order into the running u64 totals `tot`:
+//            ordered by the stream, so the chunks of a bulk pass accumulate into it.
+// All pointers at the launch's first row; `part` holds summary_part_bytes(rows, npol).
+struct SumArgs {
+  const uint32_t* words;  // [rows][npol]
+  uint64_t* planes;       // [rows][G][2], or nullptr: counters only
+  uint32_t* part;         // the workgroups' partial blocks
+  uint64_t* tot;          // [npol][KW_SUM_N], added to
+  uint64_t rows;
+  uint32_t npol;
+};
+hipError_t launch_summary(const SumArgs& a, hipStream_t s);
+// Bytes of SumArgs::part for launches of up to `rows` rows on the current device.
+size_t summary_part_bytes(uint64_t rows, uint32_t npol);
+
+// kw_batch_verdict_rows: out[i][0..row_words) = words[rows[i]][0..row_words) for n device rows.
+struct GatherArgs {
+  const uint32_t* words;
+  const uint64_t* rows;
+  uint32_t* out;
+  uint64_t n;
+  uint32_t row_words;
+};
+hipError_t launch_gather_rows(const GatherArgs& a, hipStream_t s);
 
 hipError_t launch_nfa_classify(const EvalArgs& a, const TileArgs* d_t, const NfaPass& np, uint32_t threads, hipStream_t s);
 // threads of the NFA pass's grid for `items` entities within a scratch budget

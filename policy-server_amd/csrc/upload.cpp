@@ -19,6 +19,13 @@ namespace kw {
 // geometry (plan.cpp plan_pass), and verdicts and side data are scattered back to batch rows on the host.
 constexpr uint64_t kSplitMinRows = 1ull << 18;
 
+bool page_locked(const void* p) {
+  hipPointerAttribute_t a;
+  const bool host = p && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
+  (void)hipGetLastError();  // a pageable pointer leaves an error state behind
+  return host;
+}
+
 uint64_t split_rows(const Batch& B, std::vector<uint64_t>* perm) {
   const int mode = Knobs::num<KW_SPLIT>();
   if (mode == 0 || B.n == 0) return 0;

@@ -82,6 +82,11 @@ int validate_host(const kw_env* env, kw_batch* kb, const int32_t* policies, uint
 // kw_validate_host_packed (bulk.cpp): the same pass, the verdicts in the packed form (packed.hpp).
 int validate_host_packed(const kw_env* env, kw_batch* kb, const int32_t* policies, uint32_t npol, int origin, int device,
                          kw_packed* out, uint32_t chunk_rows);
+// kw_validate_host_summary (bulk.cpp): the same pass, the summary form (summary.hpp) its only output.
+int validate_host_summary(const kw_env* env, kw_batch* kb, const int32_t* policies, uint32_t npol, int origin, int device,
+                          kw_summary* out, uint32_t chunk_rows);
+// Whether p is page-locked host memory the copy engines reach directly.
+bool page_locked(const void* p);
 // The dictionary of a packed pass, dict [npol][3] (packed.cpp): a function of the environment, the
 // policy list and the origin alone. KW_E_ARG for a policy index outside the visible policies.
 int packed_dict(const Env& E, const int32_t* policies, uint32_t npol, int origin, uint32_t* dict);

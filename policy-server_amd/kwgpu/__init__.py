@@ -383,6 +383,51 @@ class PackedVerdicts:
         return out
 
 
+class Summary:
+    """The summary form of a pass of rows x npol (kw_summary, include/kwgpu.h): `.col` uint64
+    [npol][KW_SUM_N] per-column counters (indices: kwgpu._native.KW_SUM_*), `.planes` uint64
+    [rows][G][2] with bit c of [r][g][0] set where column 64 g + c rejects and of [r][g][1] where
+    its reason is non-zero, or None with planes=False (counters only). pinned=True takes the planes
+    from page-locked memory (direct DMA), which lives as long as any view of them."""
+
+    def __init__(self, rows, npol, planes=True, pinned=False, device=0):
+        import numpy as np
+        self.rows, self.npol = int(rows), int(npol)
+        self.G = (self.npol + 63) // 64
+        self.pinned, self.device = pinned, device
+        self.col = np.zeros((self.npol, N.KW_SUM_N), dtype=np.uint64)
+        self.planes = None
+        if planes:
+            n = self.rows * self.G * 2
+            flat = PinnedWords(n * 2, device).array.view(np.uint64)[:n] if pinned else np.zeros(n, dtype=np.uint64)
+            self.planes = flat.reshape(self.rows, self.G, 2)
+
+    def _struct(self):
+        u64p = C.POINTER(C.c_uint64)
+        return N.KwSummary(self.rows, self.npol, self.col.ctypes.data_as(u64p),
+                           None if self.planes is None else self.planes.ctypes.data_as(u64p))
+
+    @classmethod
+    def from_words(cls, words, npol, planes=True):
+        """Diagnostic (kw_debug_summarize_words): full words [rows][npol] reduced on the host by the
+        reference reducer."""
+        import numpy as np
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        self = cls(words.size // npol, npol, planes=planes)
+        st = self._struct()
+        raise_for(N.lib().kw_debug_summarize_words(words.ctypes.data_as(C.POINTER(C.c_uint32)), self.rows, npol,
+                                                   C.byref(st)), "kw_debug_summarize_words failed")
+        return self
+
+    def flagged_rows(self, plane=1):
+        """The rows with a bit set in `plane` (1: a policy found something; 0: a final reject).
+        ValueError on a counters-only Summary."""
+        import numpy as np
+        if self.planes is None:
+            raise ValueError("a Summary without planes has no per-row bits")
+        return np.nonzero(self.planes[:, :, plane].any(axis=1))[0]
+
+
 class NoSpace(Exception):
     """KW_E_NOSPACE of a packed pass: the exception words exceed the capacity; .need holds them."""
 
@@ -514,12 +559,66 @@ class Batch:
             out.exc_count = st.exc_count
             if rc != N.KW_E_NOSPACE:
                 break
+            self.device, self._npol = device, npol  # (the pass ran to its end on the device)
             if not own or attempt:
                 raise NoSpace(st.exc_count)
             out._grow(st.exc_count)
         raise_for(rc, "kw_validate_host_packed failed")
         self.device = device
         self._npol = npol
+        return out
+
+    def last_pass(self):
+        """(rows, verdict words per row) of the last device pass as the library holds it
+        (kw_batch_last_pass); KW_E_ARG for a batch without one."""
+        rows, rw = C.c_uint64(), C.c_uint32()
+        raise_for(self._L.kw_batch_last_pass(self._h, C.byref(rows), C.byref(rw)), "the batch holds no device pass")
+        return rows.value, rw.value
+
+    @staticmethod
+    def _summary_out(out, rows, npol, planes):
+        """`out`, or a new Summary; `planes` None follows `out` (without `out`: with planes). A reused
+        Summary of another shape goes to the library, which answers KW_E_ARG."""
+        if out is None:
+            return Summary(rows, npol, planes=planes is None or bool(planes))
+        if planes is not None and bool(planes) != (out.planes is not None):
+            raise ValueError("planes contradicts the Summary given as out")
+        return out
+
+    def summary(self, out=None, planes=None):
+        """The summary of the last device pass (kw_batch_summary): per-column counters and, with
+        planes, the reject / found bits of every pair, reduced on the device. `out`: a reused Summary
+        of the pass's rows and columns (a validate_rows pass is one column); it decides whether planes
+        are read back, and a `planes` that contradicts it is a ValueError."""
+        out = self._summary_out(out, *self.last_pass(), planes)
+        st = out._struct()
+        raise_for(self._L.kw_batch_summary(self._h, C.byref(st)), "kw_batch_summary failed")
+        return out
+
+    def validate_host_summary(self, env, policies, out=None, origin=VALIDATE, device=0, chunk_rows=0, planes=None):
+        """The bulk pass with the summary as its only output (kw_validate_host_summary): returns a
+        Summary (`out` and `planes` as for summary()). The words stay on the device for verdict_rows() /
+        verdicts()."""
+        npol = len(policies)
+        out = self._summary_out(out, self.n, npol, planes)
+        arr = (C.c_int32 * npol)(*[env._idx(p) for p in policies])
+        st = out._struct()
+        rc = self._L.kw_validate_host_summary(env._h, self._h, arr, npol, origin, device, C.byref(st), chunk_rows)
+        raise_for(rc, "kw_validate_host_summary failed")
+        self.device = device
+        self._npol = npol
+        return out
+
+    def verdict_rows(self, rows):
+        """The full words of the chosen batch rows of the last pass (kw_batch_verdict_rows), as a
+        uint32 array [len(rows)][row words]; loads the pass's side data like verdicts()."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        # (sized by the library's own record of the pass, never by this wrapper's: the entry takes no capacity)
+        out = np.zeros((rows.size, self.last_pass()[1]), dtype=np.uint32)
+        rc = self._L.kw_batch_verdict_rows(self._h, rows.ctypes.data_as(C.POINTER(C.c_uint64)), rows.size,
+                                           out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        raise_for(rc, "kw_batch_verdict_rows failed")
         return out
 
     def debug_plan(self, env, policies, origin=VALIDATE):

@@ -42,6 +42,13 @@ KW_F_PATCH = 0x40
 KW_FST_NONE, KW_FST_VANILLA, KW_FST_MUTATION_REFUSED, KW_FST_INIT_ERROR = 0, 1, 2, 3
 KW_ARG_WIDE = 0xFFFF
 
+# kw_summary counter indices (kwgpu.h)
+KW_SUM_F_ALLOWED, KW_SUM_V_ALLOWED, KW_SUM_V_MUTATED, KW_SUM_F_PATCH, KW_SUM_BYPASS = 0, 1, 2, 3, 4
+KW_SUM_FST_VANILLA, KW_SUM_FST_MUTATION_REFUSED, KW_SUM_FST_INIT_ERROR = 5, 6, 7
+KW_SUM_REASON_OTHER = 8
+KW_SUM_REASON = 16
+KW_SUM_N = 32
+
 REASONS = {
     0: "NONE", 1: "PRIVILEGED", 2: "NAMESPACE", 3: "REG_NOT_ALLOWED", 4: "REG_REJECTED",
     5: "TAG_REJECTED", 6: "IMG_NOT_ALLOWED", 7: "IMG_REJECTED", 8: "CAP_NOT_ALLOWED",
@@ -86,6 +93,12 @@ class KwPacked(C.Structure):
                 ("dict", C.POINTER(C.c_uint32)), ("exc_count", C.c_size_t)]
 
 
+class KwSummary(C.Structure):
+    """kw_summary: the summary form (include/kwgpu.h)."""
+    _fields_ = [("rows", C.c_uint64), ("npol", C.c_uint32), ("col", C.POINTER(C.c_uint64)),
+                ("planes", C.POINTER(C.c_uint64))]
+
+
 EXPORTS = [
     "kw_env_build", "kw_env_build_yaml", "kw_yaml_to_json", "kw_env_serialize", "kw_env_deserialize", "kw_env_destroy", "kw_env_lookup",
     "kw_env_policy_count", "kw_env_policy_id", "kw_env_is_group", "kw_env_get_policy_mode",
@@ -96,7 +109,9 @@ EXPORTS = [
     "kw_debug_tile_descs", "kw_debug_tile_cost", "kw_debug_tile_slot",
     "kw_batch_from_json", "kw_batch_from_soa", "kw_batch_view", "kw_batch_to_device", "kw_batch_to_device_async",
     "kw_stream_create", "kw_stream_destroy", "kw_validate_host", "kw_validate_host_packed", "kw_packed_word",
-    "kw_packed_unpack", "kw_debug_pack_words", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
+    "kw_packed_unpack", "kw_debug_pack_words", "kw_batch_summary", "kw_validate_host_summary", "kw_batch_verdict_rows",
+    "kw_batch_last_pass",
+    "kw_debug_summarize_words", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
     "kw_batch_destroy", "kw_debug_host_walk", "kw_validate_batch", "kw_validate_rows", "kw_batch_verdicts",
     "kw_validate_timed", "kw_format_response", "kw_format_response_doc", "kw_env_group_members", "kw_evaluate",
     "kw_service_constraints", "kw_metrics_create", "kw_metrics_destroy", "kw_metrics_record", "kw_metrics_render",
@@ -170,6 +185,11 @@ def lib():
         "kw_packed_word": (ip, [C.POINTER(KwPacked), u64, u32, C.POINTER(u32)]),
         "kw_packed_unpack": (ip, [C.POINTER(KwPacked), u64, u64, C.POINTER(u32)]),
         "kw_debug_pack_words": (ip, [vp, C.POINTER(i32), u32, ip, C.POINTER(u32), u64, C.POINTER(KwPacked)]),
+        "kw_batch_summary": (ip, [vp, C.POINTER(KwSummary)]),
+        "kw_validate_host_summary": (ip, [vp, vp, C.POINTER(i32), u32, ip, ip, C.POINTER(KwSummary), u32]),
+        "kw_batch_verdict_rows": (ip, [vp, C.POINTER(u64), sz, C.POINTER(u32)]),
+        "kw_batch_last_pass": (ip, [vp, C.POINTER(u64), C.POINTER(u32)]),
+        "kw_debug_summarize_words": (ip, [C.POINTER(u32), u64, u32, C.POINTER(KwSummary)]),
         "kw_batch_pin_host": (ip, [vp, ip]),
         "kw_host_alloc": (ip, [ip, sz, C.POINTER(vp)]),
         "kw_host_free": (None, [vp]),
