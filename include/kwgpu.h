@@ -305,6 +305,25 @@ uint64_t kw_debug_tile_cost(uint32_t feat, uint32_t need, uint32_t requests, uin
  * and the descriptor the slot runs as its `tile`-th tile on the strided schedule (one only while < hi). */
 int kw_debug_tile_slot(uint64_t ndesc, uint32_t grid, uint32_t workgroup, uint32_t tile, uint64_t *out);
 
+/* Diagnostic (tests): the counter schedule with `rounds` static rounds (a slot's first `rounds` tiles
+ * strided, the rest of its XCD's range drawn from the XCD's counter), for `workgroup` as above.
+ * out[0..7): the XCD's first descriptor, the workgroup's slot, the XCD's workgroups (its static tile k
+ * is the descriptor lo + slot + k * workgroups), how many of the slot's static tiles exist, the XCD's
+ * counter-drawn tail [tail_lo, hi), and the launch's whole rounds q (the least over its XCDs of the
+ * rounds in which every slot has a tile). */
+int kw_debug_sched_tail(uint64_t ndesc, uint32_t grid, uint32_t workgroup, uint32_t rounds, uint64_t *out);
+
+/* Diagnostic (tests): the static rounds a launch of ndesc descriptors over `grid` workgroups is handed
+ * under the current KW_SCHED / KW_SCHED_TAIL (*rounds; -1: the strided schedule, no counter).
+ * dynamic: whether the launch's plan chose the dynamic schedule (kw_debug_tile_descs reports it). */
+int kw_debug_sched_rounds(uint64_t ndesc, uint32_t grid, int dynamic, int *rounds);
+
+/* Diagnostic (tests): the tile-kernel launches of the batch's last resident pass (kw_validate_batch,
+ * kw_validate_rows), three words each: the workgroups launched (the planned grid clamped to what the
+ * device holds at once), the launch's descriptors, and its static rounds (-1: strided, no counter).
+ * *needed: words; KW_E_NOSPACE when cap is smaller; KW_E_ARG for a batch that is not resident. */
+int kw_debug_last_launches(const kw_batch *b, int64_t *out, size_t cap, size_t *needed);
+
 /* Diagnostic (tests): the device-row order kw_batch_to_device gives this batch — the light / heavy
  * split (rows with more than 5 containers after the others when they are 1-50 % of
  * a batch of >= 2^18 rows and hold >= 30 % of its containers; KW_SPLIT=0 / 1 never / always) — as a

@@ -703,6 +703,7 @@ struct BulkPass {
     HIPCHK(hipStreamWaitEvent(sc, ev[3 * k], 0));
     EvalArgs Ak = A;
     Ak.ndesc = cd.size();
+    // (strided, or the counters from the third tile on: a chunk's few rounds take no counter-drawn tail)
     if (!sched_dynamic(cd.size(), pl.grid, pl.geom.lds_tables != 0)) Ak.sched = nullptr;
     if (!cd.empty()) HIPCHK(launch_evaluate_tiles(Ak, pl.tiles[0], D.d_tiles, dd, pl.grid, sc));
     return KW_OK;

@@ -686,6 +686,32 @@ int kw_debug_tile_slot(uint64_t ndesc, uint32_t grid, uint32_t workgroup, uint32
   return KW_OK;
 }
 
+int kw_debug_sched_tail(uint64_t ndesc, uint32_t grid, uint32_t workgroup, uint32_t rounds, uint64_t* out) {
+  if (!out || !grid || workgroup >= grid) return KW_E_ARG;
+  const TileSlot s = tile_slot(ndesc, grid, workgroup);
+  const uint64_t tail = tile_tail_lo(s, rounds);
+  const uint64_t first = s.t_lo + s.slot;
+  const uint64_t v[7] = {s.t_lo, s.slot, s.wpx, tail > first ? (tail - first + s.wpx - 1) / s.wpx : 0, tail, s.t_hi,
+                         tile_whole_rounds(ndesc, grid)};
+  std::copy(v, v + 7, out);
+  return KW_OK;
+}
+
+int kw_debug_sched_rounds(uint64_t ndesc, uint32_t grid, int dynamic, int* rounds) {
+  if (!rounds || !grid) return KW_E_ARG;
+  *rounds = sched_static_rounds(ndesc, grid, dynamic != 0);
+  return KW_OK;
+}
+
+int kw_debug_last_launches(const kw_batch* kb, int64_t* out, size_t cap, size_t* needed) {
+  if (!kb || !kb->dev || !needed || (!out && cap)) return KW_E_ARG;
+  const std::vector<int64_t>& v = kb->dev->last_launches;
+  *needed = v.size();
+  if (cap < v.size()) return KW_E_NOSPACE;
+  std::copy(v.begin(), v.end(), out);
+  return KW_OK;
+}
+
 int kw_debug_reorder(const kw_batch* kb, uint64_t* perm, size_t cap, uint64_t* split, kw_batch** out) {
   if (!kb || !split || !out || (!perm && kb->b.n) || cap < kb->b.n) return KW_E_ARG;
   std::vector<uint64_t> p;

@@ -558,12 +558,15 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   };
 
   const uint32_t npol = a.npol;
-  // Tile schedule (plan.cpp sched_dynamic picks one per launch). Workgroup b runs on XCD b % 8 and
-  // serves that XCD's contiguous range of tiles. Static: the range strided by the XCD's
-  // workgroups. Dynamic (a.sched): the tiles one at a time from the XCD's own
-  // counter (a 128-B line each, so no counter is shared between XCDs); the atomic for the next tile
-  // is issued when the current tile starts and its result is read only at the tile's end, so its
-  // latency hides behind the tile. The XCD's last workgroup to finish zeroes the counter again.
+  // Tile schedule (chosen per launch: plan.cpp sched_dynamic and sched_static_rounds). Workgroup b
+  // runs on XCD b % 8 and serves that XCD's contiguous range of tiles. Strided (a.sched null): the
+  // range strided by the XCD's workgroups. With counters (a.sched): a slot's first S tiles strided
+  // in the same way, then the tiles one at a time from the XCD's own counter (a 128-B line each, so
+  // no counter is shared between XCDs); S = 2 is the dynamic schedule, S = the launch's rounds less
+  // a few a strided launch with a counter-drawn tail (below, at dbase). The atomic is issued by
+  // thread 0 when the current tile starts; its value is first needed after the staging barrier,
+  // where thread 0 stores it to LDS, and every wave reads it there at the tile's end, so its
+  // latency hides behind the staging. The XCD's last workgroup to finish zeroes the counter again.
   // The schedule runs two tiles ahead: while a tile is evaluated, the index of the next one is
   // already known, so its descriptor is copied into LDS under this tile's staging (the next tile's
   // P0 and its L2 prefetch read it there, with no dependent global load), and the counter fetch
@@ -599,12 +602,20 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
     if (lane == 0u) v = atomicAdd(&l_nx[2u + k], 1u);
     return (kSlotThreads >> 6) + __builtin_amdgcn_readfirstlane(v);
   };
-  // Dynamic: a workgroup's first two tiles are static (the XCD's range in workgroup order), so a
-  // launch does not open with every workgroup's counter fetches queued on one L2 line; the counter
-  // hands out the range from its third tile-set on (value v = tile dbase + v). r05: the opening
-  // fetches cost a 1M C4 pass 2.4 % and a 64k-request shard 57 % (profiles/r05_sched_ab.txt).
+  // Dynamic: a workgroup's first S tiles (a.sched_static, chosen per launch: plan.cpp
+  // sched_static_rounds) are static (the XCD's range in workgroup order, strided), and the counter
+  // hands out the rest of the range, the tail (value v = tile dbase + v). S >= 2, so a launch does
+  // not open with every workgroup's counter fetches queued on one L2 line: r05, the opening fetches
+  // cost a 1M C4 pass 2.4 % and a 64k-request shard 57 % (profiles/r05_sched_ab.txt). A launch of
+  // many even rounds takes all but its last few static and pays the fetches only where they balance
+  // the finish. No round is counted against S, and no wave but thread 0's tells the two parts
+  // apart: the tile after `next` is static exactly while next + wpx < dbase (a slot that has left
+  // the static part never returns to it), and thread 0 hands it to the others through l_nx either
+  // way, as a signed 32-bit distance from dbase. (Testing next + wpx >= dbase again where `next`
+  // advances kept the sum in two VGPRs across the tile: every instantiation two VGPRs more, three
+  // of them a wave per SIMD fewer.)
   const uint32_t wpx = (gridDim.x - xcd + nx - 1u) / nx;  // workgroups b < gridDim.x with b % nx == xcd
-  const uint64_t dbase = t_lo + 2ull * wpx;
+  const uint64_t dbase = dyn ? t_lo + (uint64_t)a.sched_static * wpx : 0;
   uint64_t tile = t_lo + blockIdx.x / nx, next = tile + wpx;
   // the first tile's descriptor goes out with the table staging below (r06: one memory round trip
   // fewer before the first tile, which a small shard's ~2 tiles a workgroup feel; the A/B against
@@ -704,7 +715,21 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
     const uint64_t p0_t0 = timing ? clock64() : 0;
     const uint32_t cur = it & 1u;
     uint32_t nxt2 = 0;
-    if (dyn && tid == 0) nxt2 = atomicAdd(cnt, 1u);  // the tile after next (read after the staging barrier)
+    // the tile after next as thread 0 will leave it in l_nx[cur], relative to dbase (read after the
+    // staging barrier): still static, below dbase and so negative, or drawn from the counter
+    if (dyn && tid == 0) {
+      if (next + wpx >= dbase) {
+        // (the pointer through a VGPR: on a uniform address the compiler's atomic optimizer wraps the
+        // fetch in a wave reduction and a readfirstlane, which waits for the value here, a round trip
+        // to L2 at the top of every tile instead of one hidden behind the staging. A global pointer:
+        // a flat atomic would count in lgkmcnt too, and the next LDS read would wait for it.)
+        auto* c = (__attribute__((address_space(1))) uint32_t*)cnt;
+        asm volatile("" : "+v"(c));
+        nxt2 = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        nxt2 = (uint32_t)(next + wpx - dbase);
+      }
+    }
     if (next < t_hi) fetch_desc(next, cur ^ 1u);      // the next tile's descriptor (slot free since its last read)
     const TileDesc& d = l_desc[cur];
 #define KW_DF(x) sfield(x)
@@ -712,7 +737,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
       if (dyn && tid == 0) l_nx[cur] = nxt2;
       __syncthreads();  // also waits for the next descriptor
       tile = next;
-      next = dyn ? dbase + l_nx[cur] : next + wpx;
+      next = dyn ? dbase + (uint64_t)(int64_t)(int32_t)l_nx[cur] : next + wpx;
       continue;
     }
     uint64_t p0_t1 = 0, p0_t2 = 0;
@@ -1381,7 +1406,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
     if (timing) sg_add(SG_P3_WAIT, clock64() - p3_end);
     mark(4);
     tile = next;
-    next = dyn ? dbase + l_nx[cur] : next + wpx;
+    next = dyn ? dbase + (uint64_t)(int64_t)(int32_t)l_nx[cur] : next + wpx;
   }
   if (timing && tid == 0) {  // one lane's vector stores
     ph[6] = clock64() - t_begin;
@@ -1390,7 +1415,18 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   }
   if (dyn && tid == 0) {  // the XCD's last workgroup (every other one has taken its last tile) resets
     uint32_t* done = a.sched + 256u + xcd * 32u;
-    __threadfence();  // this workgroup's last counter fetch is ordered before its done count
+    // This workgroup's counter fetches come before its done count without a fence of device scope:
+    // each fetch has returned its value (the loop ended on one, the others were stored to l_nx
+    // after a vmcnt(0)), and a returning atomic of agent scope has been performed at agent scope
+    // before it returns; the done count is issued after that, and the reset below only after the
+    // last done count has returned. This is an argument from the hardware, not from the language's
+    // memory model, in which relaxed atomics on two addresses promise no such order; the compiler
+    // is held to the program order by the fence of wavefront scope. A __threadfence() here is a
+    // write-back and an invalidate of the XCD's whole L2 (buffer_wbl2 sc1, buffer_inv sc1) by every
+    // workgroup as it ends, with the launch's verdict words dirty in that L2 and the other slots'
+    // tables and next tiles cached there: it cost a C4 launch 0.013 ms at 500k requests whatever the
+    // number of fetches (profiles/r09_sched_tail_ab.txt).
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     if (atomicAdd(done, 1u) == wpx - 1u) {
       atomicExch(cnt, 0u);
       atomicExch(done, 0u);
@@ -1774,35 +1810,39 @@ hipError_t ensure_attrs() {
 }
 }  // namespace
 
+uint32_t tile_launch_grid(const TileArgs& t, bool timing, uint32_t grid, bool print) {
+  // The grid is persistent (tiles strided by gridDim.x), so it must be co-resident: a workgroup
+  // that only starts when another retires doubles the tail. Clamp the planner's grid to the
+  // runtime's occupancy for this LDS size (queried once per device and LDS size, per thread).
+  if (ensure_attrs() != hipSuccess) return grid;  // (the occupancy query needs the LDS attribute set; the launch reports the error)
+  thread_local int c_dev = -1, c_ncu = 0, c_occ = 0;
+  thread_local uint64_t c_key = ~0ull;
+  int dev = 0;
+  const uint64_t key = ((uint64_t)t.lds_bytes << 8) | ((uint64_t)tile_feat(t) << 2) | (timing ? 2u : 0u) | (t.lds_tables ? 1u : 0u);
+  if (hipGetDevice(&dev) == hipSuccess && (dev != c_dev || key != c_key)) {
+    int ncu = 0, occ = 0;
+    const void* fn = tile_fn(t.lds_tables != 0, timing, tile_feat(t));
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kSlotThreads, t.lds_bytes) != hipSuccess)
+      ncu = occ = 0;
+    c_dev = dev;
+    c_key = key;
+    c_ncu = ncu;
+    c_occ = occ;
+  }
+  // (the API's LDS bound is floor(160 KiB / bytes); the CU allocates 1280-byte granules)
+  c_occ = std::min<int>(c_occ, (int)lds_workgroups_per_cu(t.lds_bytes));
+  if (c_occ > 0 && c_ncu > 0) grid = std::max<uint32_t>(1u, std::min<uint32_t>(grid, (uint32_t)(c_occ * c_ncu)));
+  if (print && (t.debug & 256u))
+    fprintf(stderr, "[kw tile] launch grid=%u occupancy=%d wg/cu x %d CUs lds=%u\n", grid, c_occ, c_ncu, t.lds_bytes);
+  return grid;
+}
+
 hipError_t launch_evaluate_tiles(const EvalArgs& a, const TileArgs& t, const TileArgs* d_t, const TileDesc* d_desc,
                                  uint32_t grid, hipStream_t s) {
   if (a.nrows == 0 || t.nchunk == 0 || a.ndesc == 0) return hipSuccess;
   if (hipError_t e = ensure_attrs(); e != hipSuccess) return e;
-  // The grid is persistent (tiles strided by gridDim.x), so it must be co-resident: a workgroup
-  // that only starts when another retires doubles the tail. Clamp the planner's grid to the
-  // runtime's occupancy for this LDS size (queried once per device and LDS size, per thread).
-  {
-    thread_local int c_dev = -1, c_ncu = 0, c_occ = 0;
-    thread_local uint64_t c_key = ~0ull;
-    int dev = 0;
-    const uint64_t key = ((uint64_t)t.lds_bytes << 8) | ((uint64_t)tile_feat(t) << 2) | (a.phase ? 2u : 0u) | (t.lds_tables ? 1u : 0u);
-    if (hipGetDevice(&dev) == hipSuccess && (dev != c_dev || key != c_key)) {
-      int ncu = 0, occ = 0;
-      const void* fn = tile_fn(t.lds_tables != 0, a.phase != nullptr, tile_feat(t));
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kSlotThreads, t.lds_bytes) != hipSuccess)
-        ncu = occ = 0;
-      c_dev = dev;
-      c_key = key;
-      c_ncu = ncu;
-      c_occ = occ;
-    }
-    // (the API's LDS bound is floor(160 KiB / bytes); the CU allocates 1280-byte granules)
-    c_occ = std::min<int>(c_occ, (int)lds_workgroups_per_cu(t.lds_bytes));
-    if (c_occ > 0 && c_ncu > 0) grid = std::max<uint32_t>(1u, std::min<uint32_t>(grid, (uint32_t)(c_occ * c_ncu)));
-    if (t.debug & 256u)
-      fprintf(stderr, "[kw tile] launch grid=%u occupancy=%d wg/cu x %d CUs lds=%u\n", grid, c_occ, c_ncu, t.lds_bytes);
-  }
+  grid = tile_launch_grid(t, a.phase != nullptr, grid, /*print=*/true);  // (an already clamped grid stays as it is)
   using TileFn = void (*)(EvalArgs, const TileArgs*, const TileDesc*);
   const TileFn fn = (TileFn)tile_fn(t.lds_tables != 0, a.phase != nullptr, tile_feat(t));
   hipLaunchKernelGGL(fn, dim3(grid), dim3(kSlotThreads), t.lds_bytes, s, a, d_t, d_desc);

@@ -35,6 +35,7 @@ struct EvalArgs {
   const uint32_t* capdrop_off;
   uint32_t* out;
   uint32_t* sched;  // per-XCD tile counters (256 u32 + 256 u32 done counts), nullptr = static schedule
+  uint32_t sched_static;  // with sched: a slot's first S tiles are strided, the counters draw the rest (S >= 2)
   // overflow path: per-string classes in HBM (absolute entity indices), the wide-argument list
   uint16_t *g_ns, *g_aa, *g_img, *g_capadd, *g_capdrop, *g_lk, *g_lv;
   // NFA elements (kwdev.hpp DevNfa): their classes, computed by nfa_classify_kernel before the tile
@@ -234,6 +235,29 @@ KW_HD inline TileSlot tile_slot(uint64_t ndesc, uint32_t grid, uint32_t b) {
 }
 // The descriptor a slot runs as its k-th tile on the strided schedule (a tile only while < t_hi).
 KW_HD inline uint64_t tile_at(const TileSlot& s, uint32_t k) { return s.t_lo + s.slot + (uint64_t)k * s.wpx; }
+// The counter schedule with S static rounds (EvalArgs::sched_static): a slot's tiles k < S are its
+// strided ones, and the XCD's counter hands out the tail [tail_lo, t_hi) one descriptor at a time to
+// whichever slot asks next. Every descriptor of [t_lo, t_hi) is either one slot's static tile
+// (below tail_lo: slot (i - t_lo) % wpx, tile (i - t_lo) / wpx) or in the tail, never both. With
+// S above the XCD's whole rounds the tail is empty and a slot's last static tiles do not exist. (The
+// kernel fixes a slot's first two tiles before its first fetch, so it takes S >= 2 only; the
+// arithmetic holds for any S.)
+KW_HD inline uint64_t tile_tail_lo(const TileSlot& s, uint32_t S) {
+  const uint64_t lo = s.t_lo + (uint64_t)S * s.wpx;
+  return lo < s.t_hi ? lo : s.t_hi;
+}
+// Whole rounds of a launch: the least over its XCDs of the rounds in which every slot has a tile.
+// S <= tile_whole_rounds means every static tile exists.
+KW_HD inline uint64_t tile_whole_rounds(uint64_t ndesc, uint32_t grid) {
+  uint64_t q = ~0ull;
+  const uint32_t nx = grid < 8u ? grid : 8u;
+  for (uint32_t x = 0; x < nx; ++x) {
+    const TileSlot s = tile_slot(ndesc, grid, x);
+    const uint64_t r = (s.t_hi - s.t_lo) / s.wpx;
+    q = r < q ? r : q;
+  }
+  return nx ? q : 0;
+}
 
 // Estimated cost of a tile in wave-cycles, from its item counts: P1 and P2 run their items in
 // 64-lane blocks, one wave a block, and a block costs its longest chain however few lanes it fills
@@ -272,6 +296,14 @@ KW_HD constexpr TileCostW tile_cost_weights(uint32_t feat, uint32_t need) {
 // Fills T->jobs / njobs (plan.cpp) from T's LDS layout and string columns and the batch's six
 // request / container arrays cols[] = {req_flags, ctr_off, lbl_off, ctr_flags, capadd_off, capdrop_off}.
 void build_copy_jobs(TileArgs* T, const void* const cols[6]);
+
+// The grid a launch of the tile kernel really runs: the planner's, clamped to the workgroups the
+// device holds at once of the launch's instantiation (timing: the diagnostics one, whose registers
+// allow fewer) and LDS size. The kernel's schedule arithmetic is in terms of this grid (gridDim.x),
+// so what the host derives for a launch (sched_static_rounds, the phase report) takes it from here.
+// Needs the launch's device current; with no device the grid comes back as it is.
+// print: with KW_TILE_DEBUG & 256, the [kw tile] line of the launch.
+uint32_t tile_launch_grid(const TileArgs& t, bool timing, uint32_t grid, bool print = false);
 
 // One launch of the tile kernel over chunks t.chunk[0..nchunk). t: host copy (launch geometry);
 // d_t: the same TileArgs resident in device memory (read by the kernel).

@@ -18,7 +18,7 @@ namespace kw {
 enum Knob : int {
   KW_STREAM_POOL, KW_HOST_THREADS, KW_L2_PREFETCH, KW_KV_GLOBAL, KW_NO_MPACK,
   KW_BULK_DEBUG, KW_BULK_SAMPLE, KW_BULK_PACK, KW_BULK_CHUNK, KW_BULK_RAMP, KW_BULK_DIRECT, KW_BULK_DEPTH,
-  KW_SCHED, KW_SPLIT, KW_GROUP_FORM, KW_POISON_VERDICTS, KW_FLATTEN_THREADS,
+  KW_SCHED, KW_SCHED_TAIL, KW_SPLIT, KW_GROUP_FORM, KW_POISON_VERDICTS, KW_FLATTEN_THREADS,
   KW_SLOT_ROWS, KW_HEAVY_ROWS, KW_HEAVY_CTR, KW_GLOBAL_TABLES, KW_TILE_SPLIT, KW_ROUND_SPLIT,
   KW_TILE_QUANTILE, KW_TILE_DEBUG, KW_TILE_CUT,
   KW_NKNOBS
@@ -71,6 +71,7 @@ constexpr KnobRow kKnobs[KW_NKNOBS] = {
     knob_flag("KW_BULK_DIRECT", KnobKind::On, kLatched, kNoPlan, "bulk path: read back straight into pinned output"),
     knob_int("KW_BULK_DEPTH", kLatched, kNoPlan, -1, 0, INT_MAX, kClamp, "bulk path: chunks in flight (0: unbounded; unset: 2 or 3)"),
     knob_flag("KW_SCHED", KnobKind::Str, kLive, kPlans, "static / dynamic: force one tile schedule"),
+    knob_int("KW_SCHED_TAIL", kLive, kPlans, -1, 0, INT_MAX, kElseUnset, "rounds a strided launch draws from the counters at its end (0: none; unset: chosen per launch)"),
     knob_int("KW_SPLIT", kLive, kPlans, -1, INT_MIN, INT_MAX, kClamp, "0: never split light / heavy rows, 1: whenever both exist"),
     knob_flag("KW_GROUP_FORM", KnobKind::Str, kLive, kPlans, "script: compile every group expression as a script"),
     knob_flag("KW_POISON_VERDICTS", KnobKind::Off, kLive, kPlans, "fill the verdict words with a sentinel before a pass"),
@@ -94,7 +95,7 @@ constexpr bool knob_name_is(const char* a, const char* b) {
 KW_KNOB_ROW(KW_STREAM_POOL); KW_KNOB_ROW(KW_HOST_THREADS); KW_KNOB_ROW(KW_L2_PREFETCH); KW_KNOB_ROW(KW_KV_GLOBAL);
 KW_KNOB_ROW(KW_NO_MPACK); KW_KNOB_ROW(KW_BULK_DEBUG); KW_KNOB_ROW(KW_BULK_SAMPLE); KW_KNOB_ROW(KW_BULK_PACK);
 KW_KNOB_ROW(KW_BULK_CHUNK); KW_KNOB_ROW(KW_BULK_RAMP); KW_KNOB_ROW(KW_BULK_DIRECT); KW_KNOB_ROW(KW_BULK_DEPTH);
-KW_KNOB_ROW(KW_SCHED); KW_KNOB_ROW(KW_SPLIT); KW_KNOB_ROW(KW_GROUP_FORM); KW_KNOB_ROW(KW_POISON_VERDICTS);
+KW_KNOB_ROW(KW_SCHED); KW_KNOB_ROW(KW_SCHED_TAIL); KW_KNOB_ROW(KW_SPLIT); KW_KNOB_ROW(KW_GROUP_FORM); KW_KNOB_ROW(KW_POISON_VERDICTS);
 KW_KNOB_ROW(KW_FLATTEN_THREADS); KW_KNOB_ROW(KW_SLOT_ROWS); KW_KNOB_ROW(KW_HEAVY_ROWS); KW_KNOB_ROW(KW_HEAVY_CTR);
 KW_KNOB_ROW(KW_GLOBAL_TABLES); KW_KNOB_ROW(KW_TILE_SPLIT); KW_KNOB_ROW(KW_ROUND_SPLIT); KW_KNOB_ROW(KW_TILE_QUANTILE);
 KW_KNOB_ROW(KW_TILE_DEBUG); KW_KNOB_ROW(KW_TILE_CUT);

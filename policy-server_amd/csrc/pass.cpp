@@ -333,6 +333,7 @@ int prepare_pass(kw_batch* kb, PassPlan& plan, hipStream_t s, EvalArgs* out_args
     HIPCHK(hipMemsetAsync(D.sched, 0, 512 * sizeof(uint32_t), s));
   }
   A.sched = D.sched;
+  A.sched_static = 2;  // run_pass chooses per launch (sched_static_rounds)
   // side data: dense group causes, the overflow path's class arrays and wide-argument list
   if (plan.nwide) {
     if (int rc = ensure(&D.wide_groups, &D.wide_groups_cap, (size_t)(B.n * plan.nwide))) return rc;
@@ -368,8 +369,10 @@ int prepare_pass(kw_batch* kb, PassPlan& plan, hipStream_t s, EvalArgs* out_args
 }
 
 // Diagnostics (KW_TILE_DEBUG & 512): the tile kernel's per-phase clocks of one launch, summed over
-// its `grid` workgroups (ph: kPhaseWords words each).
-static void print_phase_report(size_t launch, uint32_t grid, const std::vector<uint64_t>& ph) {
+// its `grid` workgroups (ph: kPhaseWords words each). grid: the workgroups launched
+// (tile_launch_grid), not the planner's count.
+// ndesc, S: the launch's descriptors and static rounds (sched_static_rounds; -1: strided).
+static void print_phase_report(size_t launch, uint32_t grid, const std::vector<uint64_t>& ph, uint64_t ndesc, int S) {
   double sum[kPhaseWords] = {0};
   for (uint32_t g = 0; g < grid; ++g)
     for (uint32_t k = 0; k < kPhaseWords; ++k) sum[k] += (double)ph[(size_t)g * kPhaseWords + k];
@@ -428,10 +431,30 @@ static void print_phase_report(size_t launch, uint32_t grid, const std::vector<u
     stamped += (uint32_t)n;
     fprintf(stderr, " %.1f / %.1f %%", (double)(e_hi - e_lo) / 100.0, span > 0 ? 100.0 * idle / span : 0.0);
   }
-  // (r08: every fourth workgroup's start stamp reads back zero at grid 1024, which is also why
-  // [kw start] counts 768 late there; cause not found, those workgroups are left out here)
-  fprintf(stderr, " (all: %.1f %% idle; %u of %u workgroups stamped)\n", span_all > 0 ? 100.0 * idle_all / span_all : 0.0,
+  // (r08 saw a quarter of the start stamps read back zero "at grid 1024" and [kw start] count 768
+  // late: the report then took the planner's grid, while the timing instantiation of C4 holds 3
+  // workgroups a CU and launches 768. The zero stamps were workgroups that never ran. With the
+  // launched grid every workgroup is stamped; the test above stays for a stamp that does not arrive.)
+  fprintf(stderr, " (all: %.1f %% idle; %u of %u workgroups stamped)", span_all > 0 ? 100.0 * idle_all / span_all : 0.0,
           stamped, grid);
+  // tiles run per workgroup: on the strided schedule the slots of an XCD differ by one at most, with a
+  // counter-drawn tail the faster slots take more
+  uint64_t t_min = ~0ull, t_max = 0;
+  for (uint32_t q = 0; q < grid; ++q) {
+    const uint64_t n = ph[(size_t)q * kPhaseWords + 5];
+    t_min = std::min(t_min, n);
+    t_max = std::max(t_max, n);
+  }
+  fprintf(stderr, "; tiles per workgroup min %llu mean %.2f max %llu", (unsigned long long)(grid ? t_min : 0), tiles / std::max(grid, 1u),
+          (unsigned long long)t_max);
+  if (S >= 0) {
+    fprintf(stderr, "; S %d, tail tiles per XCD:", S);
+    for (uint32_t x = 0; x < nx; ++x) {
+      const TileSlot ts = tile_slot(ndesc, grid, x);
+      fprintf(stderr, " %llu", (unsigned long long)(ts.t_hi - tile_tail_lo(ts, (uint32_t)S)));
+    }
+  }
+  fprintf(stderr, "\n");
 }
 
 // One pass: prepare, the optional NFA pre-pass, the per-region launches, the overflow launch.
@@ -454,19 +477,27 @@ static int run_pass(kw_batch* kb, PassPlan& plan, bool timed, hipStream_t s) {
   // region by region (a split batch: the light rows' launches, then the heavy rows'), each over its
   // own descriptors; the overflow kernels after the last region, over the one overflow list
   const size_t nl = plan.launches.size();
+  D.last_launches.clear();
   for (size_t l = 0; l < plan.tiles.size(); ++l) {
     const size_t k = l / nl;
     if (phases) HIPCHK(hipMemsetAsync(d_phase, 0, phase_bytes, s));
-    const uint32_t grid = plan.regions[k].grid;
+    // the workgroups the launch really runs: the kernel's schedule is in terms of gridDim.x, and the
+    // planner's grid is clamped to what the device holds of this instantiation (the timing one runs
+    // C4 at 3 workgroups a CU where the product kernel runs 4)
+    const uint32_t grid = tile_launch_grid(plan.tiles[l], phases, plan.regions[k].grid);
     EvalArgs Ak = A;
     Ak.ndesc = D.reg_ndesc[k];
-    if (!plan.regions[k].dyn) Ak.sched = nullptr;  // the strided schedule
+    // the schedule, from the launch's own descriptor count and grid: strided, or S static rounds and the counters
+    const int S = sched_static_rounds(Ak.ndesc, grid, plan.regions[k].dyn);
+    if (S < 0) Ak.sched = nullptr;
+    else Ak.sched_static = (uint32_t)S;
+    for (int64_t v : {(int64_t)grid, (int64_t)Ak.ndesc, (int64_t)S}) D.last_launches.push_back(v);
     HIPCHK(launch_evaluate_tiles(Ak, plan.tiles[l], D.d_tiles + l, D.desc + D.reg_desc[k], grid, s));
     if (phases) {
       std::vector<uint64_t> ph((size_t)grid * kPhaseWords);
       HIPCHK(hipMemcpyAsync(ph.data(), d_phase, ph.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
-      print_phase_report(l, grid, ph);
+      print_phase_report(l, grid, ph, Ak.ndesc, S);
     }
     if (D.n_overflow && k + 1 == plan.regions.size()) HIPCHK(launch_overflow(A, D.d_tiles + l, D.overflow, D.n_overflow, s));
   }

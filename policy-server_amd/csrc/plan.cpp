@@ -15,18 +15,54 @@
 namespace kw {
 
 // Tile schedule of a launch of `ntiles` tiles over `grid` workgroups: the dynamic one (per-XCD
-// counters, kernels.hip) only where a workgroup runs more than 16 tiles, so that drift between
-// workgroups has room to build up; below that the strided schedule is as balanced and skips the
-// counter traffic: every fetch is an atomic on one L2 line per XCD, serialised — r05 same-box A/B
-// (profiles/r05_sched_ab.txt): strided C4 -2.4 %, C2 -6 %, C1 -40 %, a 64k-request shard -47 %; the
-// dynamic one C5 -7 % (its heavy region), C6 -2 %, C3 -2 %. KW_SCHED=static / dynamic forces one.
-// Tables read from global memory (C6) make tile costs vary with the caches: there the dynamic
-// schedule pays from 4 tiles a workgroup (C6 at 15: -2 %).
+// counters from a slot's third tile on, kernels.hip) only where a workgroup runs more than 16 tiles,
+// so that drift between workgroups has room to build up; below that the launch is strided, with a
+// counter-drawn tail where sched_static_rounds (below) gives it one. KW_SCHED=static / dynamic
+// forces one. Tables read from global memory (C6) make tile costs vary with the caches: there the
+// dynamic schedule pays from 4 tiles a workgroup (C6 at 15: -2 %).
+// The thresholds are r05's (profiles/r05_sched_ab.txt: strided C4 -2.4 %, C2 -6 %, C1 -40 %, a
+// 64k-request shard -47 %; dynamic C5 -7 %, C6 -2 %, C3 -2 %). What r05 measured as the counters'
+// cost was mostly not the fetches: r09 found a device-scope fence at every workgroup's end and a
+// wait on each fetch at the top of its tile, and removed both (profiles/r09_sched_tail_ab.txt:
+// C4 forced dynamic 0.247 -> 0.223 ms at 1M, 0.063 -> 0.042 ms at 125k, against 0.237 and 0.041
+// strided). The thresholds have not been measured again since.
 bool sched_dynamic(uint64_t ntiles, uint32_t grid, bool lds_tables) {
   const char* e = PlanKnobs::str<KW_SCHED>();
   if (!strcmp(e, "static")) return false;
   if (!strcmp(e, "dynamic")) return true;
   return ntiles > (lds_tables ? 16ull : 4ull) * std::max<uint32_t>(grid, 1);
+}
+
+// Static rounds S of a launch of `ndesc` descriptors (the launch's actual count, not the planner's
+// estimate) over `grid` workgroups, whose plan chose the dynamic schedule or not (`dyn`,
+// sched_dynamic): -1 for the strided schedule with no counter, else the S the kernel is handed with
+// the counters (EvalArgs::sched_static).
+// A launch that sched_dynamic leaves strided still finishes unevenly: its slots run at different
+// speeds, and with every tile assigned up front the launch lasts as long as its slowest slot while
+// the others stand idle (C4 at 1M under the timing build: 10.3 % of slot-time; with a tail 3.0 %). So with
+// q >= kSchedTailMinRounds whole rounds (kernels.hpp tile_whole_rounds) it runs its first
+// q - kSchedTail rounds strided and draws the tail from the counters: about kSchedTail + 2 fetches
+// a workgroup, spread out because slots reach the tail at different times.
+// The rounds are those of the grid really launched (kernels.hpp tile_launch_grid), which the kernel's
+// own arithmetic uses.
+// Same-box A/B against the parent (profiles/r09_sched_tail_ab.txt): C4 at 1M (15 rounds) -6 %,
+// at 500k (7) -6 %, C2 -5 %, C3 -8 %; tails of 2, 3 and 4 rounds and the fully dynamic schedule
+// measure alike there and a tail of 1 half as good, so the shortest that works; at 6 rounds the
+// tail is level with the strided schedule and at 4 and 5 rounds 1-2 % behind it, so those launches,
+// the multi-GPU shards of a few rounds and the bulk path's 4-round chunks stay purely strided.
+// KW_SCHED_TAIL=T forces a tail of T rounds on every launch that has two static rounds left beside
+// it (q >= T + 2: the kernel fixes a slot's first two tiles before its first fetch);
+// KW_SCHED_TAIL=0 is the choice of sched_dynamic alone; KW_SCHED=static / dynamic force theirs.
+constexpr uint32_t kSchedTail = 2, kSchedTailMinRounds = 7;
+int sched_static_rounds(uint64_t ndesc, uint32_t grid, bool dyn) {
+  const int forced = PlanKnobs::num<KW_SCHED_TAIL>();
+  const int today = dyn ? 2 : -1;
+  const char* e = PlanKnobs::str<KW_SCHED>();
+  if (!strcmp(e, "static") || !strcmp(e, "dynamic") || forced == 0 || !grid) return today;
+  const uint64_t q = tile_whole_rounds(ndesc, grid);
+  if (forced > 0) return q >= (uint64_t)forced + 2 ? (int)std::min<uint64_t>(q - (uint64_t)forced, INT_MAX) : today;
+  if (dyn || q < kSchedTailMinRounds) return today;
+  return (int)std::min<uint64_t>(q - kSchedTail, INT_MAX);
 }
 
 namespace {

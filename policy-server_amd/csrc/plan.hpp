@@ -13,6 +13,9 @@ void str_range(const Batch& B, int m, uint64_t r0, uint64_t r1, uint64_t* g0, ui
 
 // Whether a launch of `ntiles` tiles over `grid` workgroups takes the dynamic tile schedule.
 bool sched_dynamic(uint64_t ntiles, uint32_t grid, bool lds_tables);
+// The static rounds S a launch of `ndesc` descriptors is handed with the counters, -1: strided, no
+// counter. `dyn`: what sched_dynamic chose for the launch.
+int sched_static_rounds(uint64_t ndesc, uint32_t grid, bool dyn);
 
 // The wide groups among the pass's columns (plan->wide): column ids are the output column
 // (all pairs) or the rows-mode column code ((chunk << 16) | column, as rowcol holds).

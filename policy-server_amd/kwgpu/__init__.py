@@ -661,6 +661,18 @@ class Batch:
         raise_for(rc, "kw_debug_tile_descs failed")
         return out[:need.value]
 
+    def debug_last_launches(self):
+        """Diagnostic (kw_debug_last_launches): (workgroups launched, descriptors, static rounds or
+        -1) of each tile-kernel launch of the batch's last resident pass."""
+        need = C.c_size_t()
+        rc = self._L.kw_debug_last_launches(self._h, None, 0, C.byref(need))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_debug_last_launches failed")
+            return []
+        out = (C.c_int64 * need.value)()
+        raise_for(self._L.kw_debug_last_launches(self._h, out, need.value, C.byref(need)), "kw_debug_last_launches failed")
+        return [tuple(out[i:i + 3]) for i in range(0, need.value, 3)]
+
     def debug_reorder(self):
         """Diagnostic (kw_debug_reorder): the device-row order kw_batch_to_device gives this batch,
         as (batch in that order, perm, light-region rows); perm[d] is the batch row at device row d."""
