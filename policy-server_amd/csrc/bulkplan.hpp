@@ -1,6 +1,7 @@
-// bulkplan.hpp — the pure arithmetic of the bulk path (bulk.cpp): the chunk schedule, the depth
-// of chunks in flight and the packed layout of a chunk's staged ranges. No HIP, no batch, no
-// settings: values of KW_* settings come in as arguments (tests/bulkplan_check.cpp runs it on the host).
+// bulkplan.hpp — the pure arithmetic of the bulk path (bulk.cpp): the chunk schedule, the slab
+// schedule of an unchunked pass, the depth of chunks in flight and the packed layout of a chunk's
+// staged ranges. No HIP, no batch, no settings: values of KW_* settings come in as arguments
+// (tests/bulkplan_check.cpp runs it on the host).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -36,6 +37,17 @@ inline std::vector<uint64_t> chunk_bounds(uint64_t ntiles, uint64_t tile_rows, u
   for (uint64_t h : head) tb.push_back(tb.back() + h);
   for (auto it = tail.rbegin(); it != tail.rend(); ++it) tb.push_back(tb.back() + *it);
   return tb;
+}
+
+// The row slabs in which the packed and the summary form go through the verdict buffer of a pass
+// that ran unchunked: slab k covers rows [rb[k], rb[k+1]), `per_rows` rows each, at least one, and
+// enough that there are at most 240; no rows: the single bound {0}, no slab.
+inline std::vector<uint64_t> slab_bounds(uint64_t rows, uint64_t per_rows) {
+  const uint64_t slab = std::max<uint64_t>({1, per_rows, (rows + 239) / 240});
+  std::vector<uint64_t> rb;
+  for (uint64_t r = 0; r < rows; r += slab) rb.push_back(r);
+  rb.push_back(rows);
+  return rb;
 }
 
 // Pinned output: at most this many chunks in flight past the read-back (0: unbounded). Unbounded,

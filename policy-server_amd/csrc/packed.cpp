@@ -1,6 +1,6 @@
 // packed.cpp — the packed verdict form's host entries (include/kwgpu.h): the dictionary of a pass
 // from the environment, the decode functions and the host-encoder diagnostic. The arithmetic is
-// packed.hpp's; the device pass is bulk.cpp's.
+// packed.hpp's; the device pass is bulk.cpp's, its packed form bulkout.cpp's.
 #include "packed.hpp"
 
 #include "upload.hpp"

@@ -1,8 +1,8 @@
 // summary.cpp — the summary form's entries on a resident pass (include/kwgpu.h): kw_batch_summary
 // reduces the last pass's verdict words on the device and reads back the counters and the planes;
 // kw_batch_verdict_rows gathers the words of chosen rows, sized by kw_batch_last_pass; the
-// host-reducer diagnostic. The
-// arithmetic is summary.hpp's, the kernels kernels.hip's, the bulk pass bulk.cpp's.
+// host-reducer diagnostic. The arithmetic is summary.hpp's, the kernels kernels.hip's, the bulk
+// pass bulk.cpp's, its summary form bulkout.cpp's.
 #include "summary.hpp"
 
 #include <cstring>

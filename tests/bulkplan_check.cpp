@@ -1,8 +1,8 @@
 // Host check of the bulk path's arithmetic (policy-server_amd/csrc/bulkplan.hpp, the header
 // bulk.cpp runs): the chunk schedule against boundaries recorded from the loop it replaced
 // (tests/golden/bulk_chunks.txt, one case a line: ntiles tile_rows per_rows ramp : b0 b1 ...) and
-// against its properties, and the packed placement of a chunk's ranges against the slot-size
-// estimate that has to cover it.
+// against its properties, the slab schedule of an unchunked pass, and the packed placement of a
+// chunk's ranges against the slot-size estimate that has to cover it.
 // Built and run by tests/test_bulkplan.py:  g++ -O2 -std=c++17 -I policy-server_amd/csrc
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +37,21 @@ static void check_chunks(uint64_t ntiles, uint64_t rows, uint64_t per, bool ramp
   }
   if (ramp && tb.size() >= 2)
     CHECK(tb[1] == std::min(ntiles, std::max<uint64_t>(1, tper / 16)), "%llu %llu %llu: first chunk", a, b, c);
+}
+
+// The slab schedule of an unchunked pass: its properties, and `want` where the bounds are given.
+static void check_slabs(uint64_t rows, uint64_t per, const std::vector<uint64_t>* want = nullptr) {
+  const std::vector<uint64_t> rb = slab_bounds(rows, per);
+  const unsigned long long a = rows, b = per;
+  if (want) CHECK(rb == *want, "slabs %llu %llu: bounds differ from the given ones", a, b);
+  const uint64_t slab = std::max<uint64_t>({1, per, (rows + 239) / 240});
+  CHECK(!rb.empty() && rb.front() == 0 && rb.back() == rows, "slabs %llu %llu: ends", a, b);
+  CHECK(rb.size() == (rows + slab - 1) / slab + 1, "slabs %llu %llu: %zu bounds", a, b, rb.size());
+  CHECK(rb.size() - 1 <= 240, "slabs %llu %llu: %zu slabs", a, b, rb.size() - 1);  // (per above ceil(rows/240): fewer still)
+  for (size_t k = 0; k + 1 < rb.size(); ++k) {
+    CHECK(rb[k] < rb[k + 1], "slabs %llu %llu: slab %zu empty", a, b, k);
+    if (k + 2 < rb.size()) CHECK(rb[k + 1] - rb[k] == slab, "slabs %llu %llu: slab %zu not of the slab size", a, b, k);
+  }
 }
 
 static void check_pack(const std::vector<PackRange>& r, bool seen[16][5]) {
@@ -82,6 +97,20 @@ int main(int argc, char** argv) {
   }
   fclose(f);
   CHECK(cases == 14 * 2 * 5 * 2, "%zu cases read", cases);
+  // the slab schedule: four given cases, then rows x per around the 240-slab limit
+  const std::vector<uint64_t> none{0}, one{0, 100}, six{0, 512, 1024, 1536, 2048, 2560, 3000};
+  check_slabs(0, 512, &none);
+  check_slabs(100, 1000, &one);
+  check_slabs(3000, 512, &six);
+  check_slabs(1000000, 128);
+  const std::vector<uint64_t> big = slab_bounds(1000000, 128);
+  CHECK(big.size() == 241 && big[1] == 4167 && big[239] == 239 * 4167ull && big[240] == 1000000, "slabs 1000000 128");
+  cases += 4;
+  for (uint64_t rows : {1ull, 2ull, 239ull, 240ull, 241ull, 1000ull, 4097ull, 57600ull, 999983ull, 1000000ull, 5000000000ull})
+    for (uint64_t per : {0ull, 1ull, 7ull, 128ull, 512ull, 4096ull, 1ull << 20}) {
+      check_slabs(rows, per);
+      ++cases;
+    }
   CHECK(bulk_depth(-1, false) == 3 && bulk_depth(-1, true) == 2 && bulk_depth(0, true) == 0 && bulk_depth(5, false) == 5,
         "depth");
   // range lists of 1 .. 24 ranges (kMaxScatterSegs): device offsets as in a 256-B aligned image

@@ -5,7 +5,8 @@ read back. Every case checks the whole pass twice: unpack() equals the oracle's 
 the oracle's words byte for byte, which pins format, order and dictionary on the device. Chunked
 passes (the running total crossing chunks, one column with many rows per wave, partial and several
 column groups, a row count off every workgroup span), the unchunked forms, pageable and page-locked
-outputs, both origins, the capacity error and the responses formatted from word(r, c)."""
+outputs, both origins, the capacity error (chunked and in the slabs of an unchunked pass), a batch
+without rows through all three bulk forms, and the responses formatted from word(r, c)."""
 import numpy as np
 import pytest
 
@@ -143,6 +144,45 @@ def test_packed_capacity_too_small_reports_the_need():
         _same(syn.batch().validate_host_packed(env, ids, out=fit, chunk_rows=2048), ora, ref, ids)
     assert ref.exc_count > max(1024, 30000 * len(ids) // 4)  # the default capacity is too small here:
     _same(syn.batch().validate_host_packed(env, ids, chunk_rows=2048), ora, ref, ids)  # regrown, retried
+
+
+def test_packed_capacity_too_small_on_the_unchunked_path():
+    """C6 whole runs unchunked and is packed in six row slabs of 512. A capacity of a third of the
+    exceptions is exceeded in the second slab (the oracle's offsets say so), so the later slabs run
+    on without exception read-backs and count: the call reports the need, which then suffices."""
+    env, _ = _envs("c6_256")
+    ids = env.policy_ids()
+    syn, ora, ref = _oracle("c6_256", 6, 3000, 6, ids)
+    cap = ref.exc_count // 3
+    assert cap > 0 and ref.exc_count > ref.exc_off[512]  # more than one slab's share
+    assert ref.exc_off[512] <= cap < ref.exc_off[5 * 512]  # some words fit; the overflow is not left to the last slab
+    for pinned in (False, True):
+        small = K.PackedVerdicts(3000, len(ids), exc_cap=cap, pinned=pinned)
+        with pytest.raises(K.NoSpace) as e:
+            syn.batch().validate_host_packed(env, ids, out=small, chunk_rows=512)
+        assert e.value.need == ref.exc_count
+        fit = K.PackedVerdicts(3000, len(ids), exc_cap=e.value.need, pinned=pinned)
+        _same(syn.batch().validate_host_packed(env, ids, out=fit, chunk_rows=512), ora, ref, ids)
+
+
+def test_empty_batch_through_all_three_forms():
+    """No rows, C4's policies: the words form returns an empty array, the packed form no exceptions
+    and the one offset 0, the summary form all-zero counters (prefilled outputs)."""
+    env, _ = _envs("c4_64")
+    ids = env.policy_ids()
+    empty = K.Batch.from_json([])  # (SynthBatch makes no batch without rows)
+    assert empty.n == 0
+    assert empty.validate_host(env, ids).size == 0
+    p = K.PackedVerdicts(0, len(ids))
+    p.exc_off.fill(0xA5A5A5A5)
+    p.exc_count = 7
+    assert empty.validate_host_packed(env, ids, out=p) is p
+    assert p.exc_count == 0 and p.exc_off[0] == 0 and p.unpack().size == 0
+    for planes in (True, False):
+        s = K.Summary(0, len(ids), planes=planes)
+        s.col.fill(0xA5A5A5A5A5A5A5A5)
+        assert empty.validate_host_summary(env, ids, out=s) is s
+        assert not s.col.any()
 
 
 @pytest.mark.parametrize("name,scfg", [("c3_group", 3), ("c4_64", 4)])

@@ -1,7 +1,8 @@
 """The bulk path's arithmetic (policy-server_amd/csrc/bulkplan.hpp, the header bulk.cpp runs) on the
 host: the chunk boundaries equal the ones recorded from the loop the header replaced
-(tests/golden/bulk_chunks.txt) and keep their properties, and the packed placement of a chunk's
-ranges stays inside the slot-size estimate: tests/bulkplan_check.cpp."""
+(tests/golden/bulk_chunks.txt) and keep their properties, the row slabs of an unchunked pass are
+the given ones and keep theirs, and the packed placement of a chunk's ranges stays inside the
+slot-size estimate: tests/bulkplan_check.cpp."""
 import os
 import shutil
 import subprocess
@@ -17,4 +18,4 @@ def test_chunk_bounds_and_packed_placement(tmp_path):
     out = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "bulk_chunks.txt")], check=False,
                          capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
-    assert "cases 280 " in out.stdout and "failures 0" in out.stdout
+    assert "cases 361 " in out.stdout and "failures 0" in out.stdout
