@@ -421,7 +421,8 @@ int kw_debug_pack_words(const kw_env *env, const int32_t *policies, uint32_t npo
  * The same input gives the same bytes. The V_ALLOWED / V_MUTATED / INIT_ERROR counters are the
  * accepted / mutated / error counts kubewarden_policy_evaluations_total carries per policy
  * (src/metrics.rs:49-140) without the per-request attributes: the attribute sets with resource kind,
- * operation and namespace still need kw_metrics_record over the words. */
+ * operation and namespace come from kw_batch_outcomes over kw_batch_attribute_groups
+ * (kw_metrics_record_pass runs both), also on the device. */
 enum {
   KW_SUM_F_ALLOWED = 0,
   KW_SUM_V_ALLOWED = 1,
@@ -467,6 +468,45 @@ int kw_batch_last_pass(const kw_batch *b, uint64_t *rows, uint32_t *row_words);
 /* Diagnostic (tests, documents): full words [rows][npol] into the summary form on the host, by the
  * reference reducer. */
 int kw_debug_summarize_words(const uint32_t *words, uint64_t rows, uint32_t npol, kw_summary *out);
+/* The outcome of a verdict word: everything the attribute sets of kubewarden_policy_evaluations_total
+ * (src/metrics.rs:49-140) take from it. KW_OUT_INIT_ERROR for a word whose F_STATUS is
+ * KW_FST_INIT_ERROR (PolicyInitializationError, the counter only); else accepted | mutated << 1 |
+ * error_code 500 << 2 of the vanilla response, where a bypassed request is accepted, not mutated and
+ * carries no error code (service.rs:45-58), and the error code is that of a group expression that
+ * failed (KW_R_GROUP_EXPR). Codes 0-7 are that bit pattern. */
+enum {
+  KW_OUT_REJECTED = 0,
+  KW_OUT_ACCEPTED = 1,   /* bit */
+  KW_OUT_MUTATED = 2,    /* bit */
+  KW_OUT_ERROR_500 = 4,  /* bit */
+  KW_OUT_INIT_ERROR = 8,
+  KW_OUT_N = 9
+};
+/* The grouped outcome count of the batch's last device pass (kw_validate_batch, kw_validate_rows as
+ * one column, or a bulk pass), counted on the device over the words where they lie: with npol the
+ * pass's words per row (kw_batch_last_pass), out u64[ngroups][KW_OUT_N][npol] (caller-owned) gets in
+ * out[g][k][c] the rows of group g whose word in column c has outcome k. row_group[rows] gives each
+ * batch row's group id < ngroups (NULL: one group); with the ids of kw_batch_attribute_groups a
+ * counter is one series of kubewarden_policy_evaluations_total (src/metrics.rs:49-140), with any
+ * other ids, such as one per namespace, the pass / fail / mutated totals a policy report holds. Only
+ * the row list goes to the device and only the table comes back; tables beyond the KW_OUTCOME_TABLE
+ * budget (bytes, default 64 MB) are counted in consecutive group ranges. The same input gives the same
+ * bytes. KW_E_ARG for an id >= ngroups, ngroups = 0 and a batch without a pass; a pass of zero rows
+ * gives an all-zero table. */
+int kw_batch_outcomes(kw_batch *b, const uint32_t *row_group, uint32_t ngroups, uint64_t *out);
+/* Diagnostic (tests, documents): the same table from full words [rows][npol] on the host, by the
+ * reference reducer (src/metrics.rs:49-140 as above). */
+int kw_debug_outcome_words(const uint32_t *words, uint64_t rows, uint32_t npol, const uint32_t *row_group,
+                           uint32_t ngroups, uint64_t *out);
+/* The dictionary of what the attribute sets (src/metrics.rs:49-140) read from a row, host only: all
+ * raw rows (KW_REQ_RAW) are one group; every other row is keyed by (request.requestKind.kind or "",
+ * operation, whether it has a namespace, namespace), so a row without a namespace and one whose
+ * namespace is "" differ. Ids are numbered by first appearance in batch order; row_group[rows] (or
+ * NULL) gets each row's id, first_row[g] (cap entries, or NULL) the first row of group g, *ngroups
+ * the count. KW_E_NOSPACE with *ngroups filled in when cap is smaller (row_group is still written).
+ * The batch keeps the result: a second call does not rebuild it. */
+int kw_batch_attribute_groups(const kw_batch *b, uint32_t *row_group, uint64_t *first_row, size_t cap,
+                              uint32_t *ngroups);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes
@@ -553,6 +593,23 @@ void kw_metrics_destroy(kw_metrics *m);
 int kw_metrics_record(kw_metrics *m, const kw_env *env, const kw_batch *b, const uint64_t *rows,
                       const int32_t *policies, const uint32_t *verdicts, const uint64_t *latency_ms,
                       size_t n, int origin);
+/* What kw_metrics_record would add for every (row, policy) pair of a pass that all share latency_ms,
+ * from the pass's grouped outcome count instead of its words (src/metrics.rs:49-140): counts
+ * u64[ngroups][KW_OUT_N][npol] as kw_batch_outcomes gives it over the groups of
+ * kw_batch_attribute_groups, first_row[g] a row of group g (the attributes are read from it). A
+ * counter n adds n to its series of kubewarden_policy_evaluations_total and, unless its outcome is
+ * KW_OUT_INIT_ERROR, n observations of latency_ms to the histogram. The label set is built once per
+ * non-zero counter, under one lock for the call. A policy index outside the visible policies is
+ * skipped, as kw_metrics_record skips it; a first_row outside the batch is KW_E_ARG. Host only. */
+int kw_metrics_add_outcomes(kw_metrics *m, const kw_env *env, const kw_batch *b, const int32_t *policies,
+                            uint32_t npol, int origin, uint64_t latency_ms, const uint64_t *first_row,
+                            uint32_t ngroups, const uint64_t *counts);
+/* The metrics of the batch's last all-pairs device pass over `policies` (src/metrics.rs:49-140):
+ * kw_batch_attribute_groups, kw_batch_outcomes, kw_metrics_add_outcomes. Only the table crosses
+ * PCIe. KW_E_ARG when npol is not the pass's words per row, after a kw_validate_rows pass (its one
+ * column has a policy per row) and for a batch without a pass. */
+int kw_metrics_record_pass(kw_metrics *m, const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol,
+                           int origin, uint64_t latency_ms);
 /* Prometheus text exposition (format 0.0.4) of everything recorded so far. */
 int kw_metrics_render(const kw_metrics *m, char *buf, size_t cap, size_t *need);
 void kw_metrics_reset(kw_metrics *m);

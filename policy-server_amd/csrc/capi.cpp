@@ -856,6 +856,33 @@ int kw_metrics_record(kw_metrics* m, const kw_env* env, const kw_batch* b, const
   return KW_OK;
 }
 
+int kw_metrics_add_outcomes(kw_metrics* m, const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol,
+                            int origin, uint64_t latency_ms, const uint64_t* first_row, uint32_t ngroups,
+                            const uint64_t* counts) {
+  if (!m || !env || !b || !policies || npol == 0 || (ngroups && (!first_row || !counts))) return KW_E_ARG;
+  if (origin != KW_ORIGIN_VALIDATE && origin != KW_ORIGIN_AUDIT) return KW_E_ARG;
+  return m->m.add_outcomes(env->e, b->b, policies, npol, origin, latency_ms, first_row, ngroups, counts) ? KW_OK : KW_E_ARG;
+}
+
+int kw_metrics_record_pass(kw_metrics* m, const kw_env* env, kw_batch* b, const int32_t* policies, uint32_t npol,
+                           int origin, uint64_t latency_ms) {
+  uint64_t rows = 0;
+  uint32_t rw = 0;
+  if (!m || !env || !policies || kw_batch_last_pass(b, &rows, &rw) != KW_OK) return KW_E_ARG;
+  if (origin != KW_ORIGIN_VALIDATE && origin != KW_ORIGIN_AUDIT) return KW_E_ARG;
+  // an all-pairs pass over these policies: a kw_validate_rows pass has a policy per row in its one column
+  if (b->dev->last_rows_mode || rw != npol || rows != b->b.n) return KW_E_ARG;
+  uint32_t ngroups = 0;
+  std::vector<uint32_t> row_group((size_t)rows);
+  (void)kw_batch_attribute_groups(b, nullptr, nullptr, 0, &ngroups);  // (the count; built once per batch)
+  std::vector<uint64_t> first_row(ngroups);
+  if (int rc = kw_batch_attribute_groups(b, row_group.data(), first_row.data(), first_row.size(), &ngroups)) return rc;
+  if (ngroups == 0) return KW_OK;  // no rows
+  std::vector<uint64_t> counts((size_t)ngroups * KW_OUT_N * npol);
+  if (int rc = kw_batch_outcomes(b, row_group.data(), ngroups, counts.data())) return rc;
+  return kw_metrics_add_outcomes(m, env, b, policies, npol, origin, latency_ms, first_row.data(), ngroups, counts.data());
+}
+
 int kw_metrics_render(const kw_metrics* m, char* buf, size_t cap, size_t* need) {
   if (!m) return KW_E_ARG;
   return put_out(m->m.render(), buf, cap, need);

@@ -126,8 +126,17 @@ struct DeviceBatch {
   // region's rows (0: not split); dev_b: the reordered batch the planner reads (its offsets only:
   // the string bytes are dropped after the upload).
   std::vector<uint64_t> perm;
-  std::vector<uint64_t> inv_perm;  // the device row of each batch row (kw_batch_verdict_rows builds it once)
+  std::vector<uint64_t> inv_perm;  // the device row of each batch row (device_rows builds it once)
   uint64_t split = 0;
+  // The device row of each batch row of a split batch, for the entries that take batch rows and
+  // index device buffers (kw_batch_verdict_rows, kw_batch_outcomes).
+  const std::vector<uint64_t>& device_rows() {
+    if (inv_perm.size() != perm.size()) {
+      inv_perm.resize(perm.size());
+      for (uint64_t d = 0; d < perm.size(); ++d) inv_perm[perm[d]] = d;
+    }
+    return inv_perm;
+  }
   std::unique_ptr<Batch> dev_b;
   // the last all-pairs pass's plan (pass.cpp validate_cached): reused while the
   // environment, the policy list, the origin and every KW_* setting stay the same — planning a
@@ -244,6 +253,15 @@ struct kw_batch {
   kw::Batch b;
   std::unique_ptr<kw::DeviceBatch> dev;
   std::vector<void*> host_pinned;  // kw_batch_pin_host: column arrays page-locked in place
+  // kw_batch_attribute_groups: the dictionary of the rows' metrics attributes, built once (the
+  // columns of a batch do not change after it is made)
+  struct AttrGroups {
+    std::mutex m;
+    bool built = false;
+    std::vector<uint32_t> row_group;
+    std::vector<uint64_t> first_row;
+  };
+  mutable AttrGroups attr;
   ~kw_batch() {
     dev.reset();  // synchronizes the batch's streams: no copy can still read a registered column
     for (void* p : host_pinned) (void)hipHostUnregister(p);

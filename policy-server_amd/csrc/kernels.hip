@@ -2185,6 +2185,59 @@ hipError_t launch_gather_rows(const GatherArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- grouped outcome count (kernels.hpp OutcomeArgs, outcomes.hpp) -------------------------------
+
+__global__ void __launch_bounds__(256) outcomes_kernel(OutcomeArgs a, PackGeom p) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, grp = blockIdx.y;
+  const uint32_t unit = blockIdx.x * kOutWaves + wave;  // wave-uniform
+  if (unit >= a.nunits) return;
+  const OutUnit u = a.units[unit];
+  const uint32_t rounds = out_rounds(p, u.n);
+  uint32_t cnt[KW_OUT_N];
+#pragma unroll
+  for (uint32_t k = 0; k < (uint32_t)KW_OUT_N; ++k) cnt[k] = 0;
+  for (uint32_t t0 = 0; t0 < rounds; t0 += kOutLoads) {  // wave-uniform
+    // the rows of kOutLoads rounds first, then their words: that many loads in flight per lane
+    uint32_t row[kOutLoads], x[kOutLoads], onm = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kOutLoads; ++i) {
+      const OutLane L = out_lane(p, a.npol, grp, u.n, t0 + i, lane);
+      row[i] = L.on ? a.order[u.first + L.entry] : 0u;
+      onm |= (L.on ? 1u : 0u) << i;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kOutLoads; ++i)
+      x[i] = (onm >> i) & 1u ? __builtin_nontemporal_load(a.words + (uint64_t)row[i] * a.npol + (64u * grp + lane % p.w)) : 0u;
+#pragma unroll
+    for (uint32_t i = 0; i < kOutLoads; ++i) {
+      const uint32_t code = (onm >> i) & 1u ? outcome_code(x[i]) : (uint32_t)KW_OUT_N;
+#pragma unroll
+      for (uint32_t k = 0; k < (uint32_t)KW_OUT_N; ++k) cnt[k] += code == k ? 1u : 0u;
+    }
+  }
+  // the unit into the table: a counter no lane holds is skipped by the whole wave; the lanes that
+  // share a column (npol <= 32: lane c + s * w holds column c's rows of sub-row s) are summed into
+  // lane c, whose adds of one outcome lie side by side in the table
+  const uint32_t sub = lane / p.w, c = lane % p.w, col = 64u * grp + c;
+  uint64_t* row_k = a.table + (uint64_t)(u.group - a.g0) * KW_OUT_N * a.npol + col;
+#pragma unroll
+  for (uint32_t k = 0; k < (uint32_t)KW_OUT_N; ++k) {
+    if (!__ballot(cnt[k] != 0u)) continue;  // wave-uniform
+    uint32_t tot = cnt[k];
+    for (uint32_t s = 1; s < p.ipi; ++s) tot += (uint32_t)__shfl((int)cnt[k], (int)((c + s * p.w) & 63u));
+    if (sub == 0u && col < a.npol && tot)
+      __hip_atomic_fetch_add(row_k + (uint64_t)k * a.npol, (uint64_t)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+hipError_t launch_outcomes(const OutcomeArgs& a, hipStream_t s) {
+  if (a.nunits == 0 || a.npol == 0) return hipSuccess;
+  const uint32_t G = packed_groups(a.npol);
+  if (G > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(outcomes_kernel, dim3((a.nunits + kOutWaves - 1u) / kOutWaves, G), dim3(256), 0, s, a, pack_geom(a.npol));
+  return hipGetLastError();
+}
+
 hipError_t launch_overflow(const EvalArgs& a, const TileArgs* d_t, const uint32_t* d_overflow, uint32_t n_overflow,
                            hipStream_t s) {
   if (n_overflow == 0 || a.nrows == 0) return hipSuccess;

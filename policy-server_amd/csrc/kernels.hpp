@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "kwdev.hpp"
+#include "outcomes.hpp"
 #include "packed.hpp"
 #include "slots.hpp"
 #include "summary.hpp"
@@ -454,6 +455,25 @@ struct GatherArgs {
   uint32_t row_words;
 };
 hipError_t launch_gather_rows(const GatherArgs& a, hipStream_t s);
+
+// The grouped outcome count (kw_batch_outcomes; the outcome, the sort and the unit table:
+// outcomes.hpp): one pass over the verdict words, gathered by whole rows in group order. A wave takes
+// one unit (one group's run of at most kOutUnitRows sorted entries), grid.y the column groups of 64;
+// a lane keeps one column (pack_geom's w lanes a row, ipi rows a load where npol <= 32), kOutLoads row
+// loads in flight and the nine outcome counters in registers by compare-and-add. After its unit the
+// wave adds the counters some lane holds to the u64 table with relaxed agent-scope vector atomics:
+// one outcome's adds are contiguous, the lanes that share a column are summed by shuffles first.
+// No LDS memory, no fence: the stream orders the table's zeroing before and its read-back after. Integer
+// adds, so the table does not depend on the order in which the waves arrive.
+struct OutcomeArgs {
+  const uint32_t* words;  // [rows][npol], device-row order
+  const uint32_t* order;  // device rows sorted by group (every entry < rows)
+  const OutUnit* units;   // this launch's units (first / n index `order`)
+  uint64_t* table;        // [groups of the range][KW_OUT_N][npol], added to
+  uint32_t nunits, npol;
+  uint32_t g0;            // the range's first group: unit group g counts into table row g - g0
+};
+hipError_t launch_outcomes(const OutcomeArgs& a, hipStream_t s);
 
 hipError_t launch_nfa_classify(const EvalArgs& a, const TileArgs* d_t, const NfaPass& np, uint32_t threads, hipStream_t s);
 // threads of the NFA pass's grid for `items` entities within a scratch budget

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include "outcomes.hpp"
+
 namespace kw {
 
 constexpr uint64_t Metrics::kBounds[];
@@ -25,32 +27,23 @@ void put_label(std::string* o, bool first, const char* key, std::string_view v) 
 
 }  // namespace
 
-void Metrics::record(const Env& env, const Batch& b, uint64_t row, int32_t policy, uint32_t v, int origin,
-                     uint64_t latency_ms) {
-  if (policy < 0 || (size_t)policy >= env.nvisible || row >= b.n) return;
+// The label set of one series: the policy's attributes, the row's, and the outcome of the word
+// (outcomes.hpp outcome_code). The one place that knows the reference's attribute keys and their
+// order; record and add_outcomes both build their keys here.
+std::string Metrics::label_set(const Env& env, const Batch& b, uint64_t row, int32_t policy, uint32_t outcome, int origin) {
   const PolicyRec& P = env.pol[(size_t)policy];
-  const bool raw = (b.req_flags[row] & KW_REQ_RAW) != 0;
-  const uint32_t fst = (v & KW_F_STATUS_MASK) >> KW_F_STATUS_SHIFT;
   std::string key;
-  if (fst == KW_FST_INIT_ERROR) {
+  if (outcome == KW_OUT_INIT_ERROR) {
     // PolicyInitializationError (metrics.rs:125-140; service.rs:78-84): the counter only
     put_label(&key, true, "policy_name", P.id);
     put_label(&key, false, "initialization_error", P.init_message);
-    std::lock_guard<std::mutex> g(mu_);
-    ++total_[key];
-    return;
+    return key;
   }
+  const bool raw = (b.req_flags[row] & KW_REQ_RAW) != 0;
   const char* mode = P.mode == KW_MODE_MONITOR ? "monitor" : "protect";  // config.rs:296-302
-  bool accepted, mutated;
-  int error_code = -1;
-  if (v & KW_BYPASS) {  // service.rs:45-58: accepted, not mutated, no error code
-    accepted = true;
-    mutated = false;
-  } else {  // the vanilla response (service.rs:97-105)
-    accepted = (v & KW_V_ALLOWED) != 0;
-    mutated = (v & KW_V_MUTATED) != 0;
-    if (KW_REASON(v) == KW_R_GROUP_EXPR) error_code = 500;  // reject(uid, rhai error, 500)
-  }
+  // a bypass (service.rs:45-58) is accepted, not mutated, no error code; else the vanilla response
+  // (service.rs:97-105), error code 500 for reject(uid, rhai error, 500): outcome_code
+  const bool accepted = (outcome & KW_OUT_ACCEPTED) != 0, mutated = (outcome & KW_OUT_MUTATED) != 0;
   put_label(&key, true, "policy_name", P.id);
   put_label(&key, false, "policy_mode", mode);
   if (raw) {  // RawPolicyEvaluation (metrics.rs:96-123)
@@ -64,14 +57,44 @@ void Metrics::record(const Env& env, const Batch& b, uint64_t row, int32_t polic
     put_label(&key, false, "request_origin", origin == KW_ORIGIN_AUDIT ? "audit" : "validate");
     if (b.req_flags[row] & KW_REQ_HAS_NAMESPACE) put_label(&key, false, "resource_namespace", b.ns.at(row));
   }
-  if (error_code >= 0) put_label(&key, false, "error_code", std::to_string(error_code));
-  std::lock_guard<std::mutex> g(mu_);
-  ++total_[key];
+  if (outcome & KW_OUT_ERROR_500) put_label(&key, false, "error_code", "500");
+  return key;
+}
+
+// n data points of one series (the caller holds mu_).
+void Metrics::add_locked(const std::string& key, uint32_t outcome, uint64_t n, uint64_t latency_ms) {
+  total_[key] += n;
+  if (outcome == KW_OUT_INIT_ERROR) return;
   Hist& h = latency_[key];
   const size_t k = std::lower_bound(kBounds, kBounds + kNB, latency_ms) - kBounds;  // first bound >= latency
-  ++h.bucket[k];
-  h.sum += latency_ms;
-  ++h.count;
+  h.bucket[k] += n;
+  h.sum += n * latency_ms;
+  h.count += n;
+}
+
+void Metrics::record(const Env& env, const Batch& b, uint64_t row, int32_t policy, uint32_t v, int origin,
+                     uint64_t latency_ms) {
+  if (policy < 0 || (size_t)policy >= env.nvisible || row >= b.n) return;
+  const uint32_t outcome = outcome_code(v);
+  const std::string key = label_set(env, b, row, policy, outcome, origin);
+  std::lock_guard<std::mutex> g(mu_);
+  add_locked(key, outcome, 1, latency_ms);
+}
+
+bool Metrics::add_outcomes(const Env& env, const Batch& b, const int32_t* policies, uint32_t npol, int origin,
+                           uint64_t latency_ms, const uint64_t* first_row, uint32_t ngroups, const uint64_t* counts) {
+  for (uint32_t g = 0; g < ngroups; ++g)
+    if (first_row[g] >= b.n) return false;
+  std::lock_guard<std::mutex> lock(mu_);
+  for (uint32_t g = 0; g < ngroups; ++g)
+    for (uint32_t k = 0; k < (uint32_t)KW_OUT_N; ++k) {
+      const uint64_t* n = counts + ((size_t)g * KW_OUT_N + k) * npol;
+      for (uint32_t c = 0; c < npol; ++c) {
+        if (!n[c] || policies[c] < 0 || (size_t)policies[c] >= env.nvisible) continue;
+        add_locked(label_set(env, b, first_row[g], policies[c], k, origin), k, n[c], latency_ms);
+      }
+    }
+  return true;
 }
 
 std::string Metrics::render() const {

@@ -26,6 +26,12 @@ class Metrics {
   // `latency_ms` the time from the request's arrival to its verdict (service.rs:37, :97).
   void record(const Env& env, const Batch& b, uint64_t row, int32_t policy, uint32_t verdict, int origin,
               uint64_t latency_ms);
+  // What `record` would add for every pair of a pass whose pairs share latency_ms, from the pass's
+  // grouped outcome count (outcomes.hpp): counts [ngroups][KW_OUT_N][npol], first_row[g] a row with
+  // group g's attributes. One lock, one label set per non-zero counter. False (nothing added) when a
+  // first_row lies outside the batch.
+  bool add_outcomes(const Env& env, const Batch& b, const int32_t* policies, uint32_t npol, int origin, uint64_t latency_ms,
+                    const uint64_t* first_row, uint32_t ngroups, const uint64_t* counts);
   std::string render() const;  // Prometheus text exposition format 0.0.4
   void reset();
 
@@ -38,6 +44,8 @@ class Metrics {
     uint64_t bucket[kNB + 1] = {};  // per-bucket counts; the last is (10000, +inf)
     uint64_t sum = 0, count = 0;
   };
+  static std::string label_set(const Env& env, const Batch& b, uint64_t row, int32_t policy, uint32_t outcome, int origin);
+  void add_locked(const std::string& key, uint32_t outcome, uint64_t n, uint64_t latency_ms);
   mutable std::mutex mu_;
   std::map<std::string, uint64_t> total_;  // label set -> kubewarden_policy_evaluations_total
   std::map<std::string, Hist> latency_;    // label set -> latency histogram

@@ -33,6 +33,32 @@ int ensure(T** p, size_t* cap, size_t n) {
   return KW_OK;
 }
 
+// Diagnostics (KW_BULK_DEBUG): the device time between two points of a stream, by timing events of
+// its own; off, every call is a no-op (summary.cpp, outcomes.cpp print it: scripts/metrics_pass_bench.py).
+struct StreamTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  bool on;
+  explicit StreamTimer(bool want) : on(want) {
+    if (on) on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
+  }
+  StreamTimer(const StreamTimer&) = delete;
+  ~StreamTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  void start(hipStream_t s) {
+    if (on) (void)hipEventRecord(a, s);
+  }
+  void stop(hipStream_t s) {
+    if (on) (void)hipEventRecord(b, s);
+  }
+  double ms() {  // (waits for the second point)
+    float t = 0;
+    if (on && hipEventSynchronize(b) == hipSuccess) (void)hipEventElapsedTime(&t, a, b);
+    return t;
+  }
+};
+
 // The environment's compiled tables to `device` (< 0: host only).
 int upload_env(kw_env* env, int device);
 

@@ -5,9 +5,11 @@
 // pass bulk.cpp's, its summary form bulkout.cpp's.
 #include "summary.hpp"
 
+#include <cstdio>
 #include <cstring>
 
 #include "kernels.hpp"
+#include "knobs.hpp"
 #include "pass.hpp"
 #include "upload.hpp"
 
@@ -50,6 +52,8 @@ int batch_summary(kw_batch* b, kw_summary* out) {
   HIPCHK(htot.alloc(host_pool(), D.device, b_tot));
   HIPCHK(dpart.alloc(dev_pool(), D.device, std::max<size_t>(summary_part_bytes(rows, npol), 256)));
   if (planes) HIPCHK(dplanes.alloc(dev_pool(), D.device, b_planes));
+  StreamTimer timer(Knobs::on<KW_BULK_DEBUG>());
+  timer.start(s);
   HIPCHK(hipMemsetAsync(dtot.p, 0, b_tot, s));
   SumArgs a;
   a.words = D.verdicts;
@@ -59,6 +63,7 @@ int batch_summary(kw_batch* b, kw_summary* out) {
   a.rows = rows;
   a.npol = npol;
   HIPCHK(launch_summary(a, s));
+  timer.stop(s);
   HIPCHK(hipMemcpyAsync(htot.p, dtot.p, b_tot, hipMemcpyDeviceToHost, s));
   if (planes && !D.split && page_locked(out->planes)) {
     HIPCHK(hipMemcpyAsync(out->planes, dplanes.p, b_planes, hipMemcpyDeviceToHost, s));
@@ -83,6 +88,9 @@ int batch_summary(kw_batch* b, kw_summary* out) {
     }
   }
   HIPCHK(hipStreamSynchronize(s));
+  if (timer.on)
+    fprintf(stderr, "[kw summary] %llu rows x %u%s: zero + reduce %.3f ms on the device\n", (unsigned long long)rows, npol,
+            planes ? ", planes" : "", timer.ms());
   memcpy(out->col, htot.p, b_tot);
   return KW_OK;
 }
@@ -97,10 +105,7 @@ int batch_verdict_rows(kw_batch* b, const uint64_t* rows, size_t n, uint32_t* ou
   DeviceBatch& D = *b->dev;
   HIPCHK(hipSetDevice(D.device));
   hipStream_t s = D.cur ? D.cur : D.stream;
-  if (D.split && D.inv_perm.size() != D.perm.size()) {
-    D.inv_perm.resize(D.perm.size());
-    for (uint64_t d = 0; d < D.perm.size(); ++d) D.inv_perm[D.perm[d]] = d;
-  }
+  if (D.split) D.device_rows();
   const size_t b_idx = n * 8, b_out = n * (size_t)rw * 4;
   BlockLease didx, dout, hidx, hout;
   Drain drain{s};

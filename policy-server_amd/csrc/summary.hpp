@@ -8,7 +8,7 @@
 // What the counters replace: the accepted / mutated / error counts of
 // kubewarden_policy_evaluations_total (src/metrics.rs:49-140) per policy are col[c][KW_SUM_V_ALLOWED],
 // [KW_SUM_V_MUTATED] and [KW_SUM_FST_INIT_ERROR] / [KW_SUM_REASON + r]; the attribute sets with the
-// per-request kind / operation / namespace still need kw_metrics_record over the words themselves.
+// per-request kind / operation / namespace are counted by kw_batch_outcomes (outcomes.hpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>

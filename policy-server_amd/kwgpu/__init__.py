@@ -621,6 +621,62 @@ class Batch:
         raise_for(rc, "kw_batch_verdict_rows failed")
         return out
 
+    def attribute_groups(self):
+        """The dictionary of the rows' metrics attributes (kw_batch_attribute_groups), host only:
+        (row_group uint32 [rows], first_row uint64 [groups]); ids by first appearance."""
+        import numpy as np
+        n = C.c_uint32()
+        row_group = np.zeros(self.n, dtype=np.uint32)
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        rc = self._L.kw_batch_attribute_groups(self._h, row_group.ctypes.data_as(u32p), None, 0, C.byref(n))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_batch_attribute_groups failed")
+        first_row = np.zeros(n.value, dtype=np.uint64)
+        raise_for(self._L.kw_batch_attribute_groups(self._h, row_group.ctypes.data_as(u32p), first_row.ctypes.data_as(u64p),
+                                                    first_row.size, C.byref(n)), "kw_batch_attribute_groups failed")
+        return row_group, first_row
+
+    def outcomes(self, row_group=None, ngroups=None):
+        """The grouped outcome count of the last device pass (kw_batch_outcomes), counted on the
+        device: uint64 [ngroups][KW_OUT_N][row words]. row_group: a group id per batch row (None: one
+        group); ngroups defaults to the largest id + 1."""
+        import numpy as np
+        rw = self.last_pass()[1]
+        if row_group is None:
+            ngroups, ptr = 1 if ngroups is None else ngroups, None
+        else:
+            row_group = np.ascontiguousarray(row_group, dtype=np.uint32).reshape(-1)
+            if row_group.size != self.n:
+                raise ValueError("row_group must hold one id per batch row")
+            if ngroups is None:
+                ngroups = int(row_group.max()) + 1 if row_group.size else 1
+            ptr = row_group.ctypes.data_as(C.POINTER(C.c_uint32))
+        out = np.zeros((ngroups, N.KW_OUT_N, rw), dtype=np.uint64)
+        raise_for(self._L.kw_batch_outcomes(self._h, ptr, ngroups, out.ctypes.data_as(C.POINTER(C.c_uint64))),
+                  "kw_batch_outcomes failed")
+        return out
+
+    @staticmethod
+    def outcomes_from_words(words, npol, row_group=None, ngroups=None):
+        """Diagnostic (kw_debug_outcome_words): the same table from full words [rows][npol] by the
+        reference host reducer."""
+        import numpy as np
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        rows = words.size // npol
+        ptr = None
+        if row_group is not None:
+            row_group = np.ascontiguousarray(row_group, dtype=np.uint32).reshape(-1)
+            if row_group.size != rows:
+                raise ValueError("row_group must hold one id per row")
+            ptr = row_group.ctypes.data_as(C.POINTER(C.c_uint32))
+            if ngroups is None:
+                ngroups = int(row_group.max()) + 1 if rows else 1
+        ngroups = 1 if ngroups is None else ngroups
+        out = np.zeros((ngroups, N.KW_OUT_N, npol), dtype=np.uint64)
+        raise_for(N.lib().kw_debug_outcome_words(words.ctypes.data_as(C.POINTER(C.c_uint32)), rows, npol, ptr, ngroups,
+                                                 out.ctypes.data_as(C.POINTER(C.c_uint64))), "kw_debug_outcome_words failed")
+        return out
+
     def debug_plan(self, env, policies, origin=VALIDATE):
         """Diagnostic (kw_debug_plan): the tile kernel's plan for an all-pairs pass, on the host."""
         arr = env._array(policies)
@@ -776,6 +832,27 @@ class Metrics:
         v = (C.c_uint32 * max(n, 1))(*[int(x) for x in verdicts])
         lat = (C.c_uint64 * max(n, 1))(*[int(x) for x in latency_ms])
         raise_for(self._L.kw_metrics_record(self._h, env._h, batch._h, r, p, v, lat, n, origin), "kw_metrics_record")
+
+    def add_outcomes(self, env, batch, policies, counts, first_row, latency_ms=0, origin=VALIDATE):
+        """What record() would add for every pair of a pass (kw_metrics_add_outcomes), from its
+        grouped outcome count: counts uint64 [groups][KW_OUT_N][policies] over the groups of
+        batch.attribute_groups(), first_row their first rows; every pair with latency_ms."""
+        import numpy as np
+        npol = len(policies)
+        first_row = np.ascontiguousarray(first_row, dtype=np.uint64).reshape(-1)
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if counts.size != first_row.size * N.KW_OUT_N * npol:
+            raise ValueError("counts must be [groups][KW_OUT_N][policies]")
+        u64p = C.POINTER(C.c_uint64)
+        raise_for(self._L.kw_metrics_add_outcomes(self._h, env._h, batch._h, env._array(policies), npol, origin, int(latency_ms),
+                                                  first_row.ctypes.data_as(u64p), first_row.size, counts.ctypes.data_as(u64p)),
+                  "kw_metrics_add_outcomes")
+
+    def record_pass(self, env, batch, policies, latency_ms=0, origin=VALIDATE):
+        """The metrics of the batch's last all-pairs device pass over `policies`
+        (kw_metrics_record_pass): dictionary on the host, count on the device, fold on the host."""
+        raise_for(self._L.kw_metrics_record_pass(self._h, env._h, batch._h, env._array(policies), len(policies), origin,
+                                                 int(latency_ms)), "kw_metrics_record_pass")
 
     def render(self):
         need = C.c_size_t(0)

@@ -32,6 +32,8 @@ KW_ORIGIN_AUDIT = 1
 KW_DOC_ADMISSION_REVIEW = 0
 KW_DOC_RAW_REVIEW = 1
 
+KW_REQ_RAW, KW_REQ_HAS_NAMESPACE, KW_REQ_HAS_PODSPEC, KW_REQ_HAS_OBJECT = 1, 2, 4, 8
+
 KW_V_ALLOWED = 0x1
 KW_V_MUTATED = 0x2
 KW_F_ALLOWED = 0x4
@@ -48,6 +50,10 @@ KW_SUM_FST_VANILLA, KW_SUM_FST_MUTATION_REFUSED, KW_SUM_FST_INIT_ERROR = 5, 6, 7
 KW_SUM_REASON_OTHER = 8
 KW_SUM_REASON = 16
 KW_SUM_N = 32
+
+# outcome codes of a verdict word (kwgpu.h): accepted | mutated << 1 | error 500 << 2, or the init error
+KW_OUT_REJECTED, KW_OUT_ACCEPTED, KW_OUT_MUTATED, KW_OUT_ERROR_500, KW_OUT_INIT_ERROR = 0, 1, 2, 4, 8
+KW_OUT_N = 9
 
 REASONS = {
     0: "NONE", 1: "PRIVILEGED", 2: "NAMESPACE", 3: "REG_NOT_ALLOWED", 4: "REG_REJECTED",
@@ -111,7 +117,8 @@ EXPORTS = [
     "kw_stream_create", "kw_stream_destroy", "kw_validate_host", "kw_validate_host_packed", "kw_packed_word",
     "kw_packed_unpack", "kw_debug_pack_words", "kw_batch_summary", "kw_validate_host_summary", "kw_batch_verdict_rows",
     "kw_batch_last_pass",
-    "kw_debug_summarize_words", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
+    "kw_debug_summarize_words", "kw_batch_outcomes", "kw_debug_outcome_words", "kw_batch_attribute_groups",
+    "kw_metrics_add_outcomes", "kw_metrics_record_pass", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
     "kw_batch_destroy", "kw_debug_host_walk", "kw_validate_batch", "kw_validate_rows", "kw_batch_verdicts",
     "kw_validate_timed", "kw_format_response", "kw_format_response_doc", "kw_env_group_members", "kw_evaluate",
     "kw_service_constraints", "kw_metrics_create", "kw_metrics_destroy", "kw_metrics_record", "kw_metrics_render",
@@ -193,6 +200,11 @@ def lib():
         "kw_batch_verdict_rows": (ip, [vp, C.POINTER(u64), sz, C.POINTER(u32)]),
         "kw_batch_last_pass": (ip, [vp, C.POINTER(u64), C.POINTER(u32)]),
         "kw_debug_summarize_words": (ip, [C.POINTER(u32), u64, u32, C.POINTER(KwSummary)]),
+        "kw_batch_outcomes": (ip, [vp, C.POINTER(u32), u32, C.POINTER(u64)]),
+        "kw_debug_outcome_words": (ip, [C.POINTER(u32), u64, u32, C.POINTER(u32), u32, C.POINTER(u64)]),
+        "kw_batch_attribute_groups": (ip, [vp, C.POINTER(u32), C.POINTER(u64), sz, C.POINTER(u32)]),
+        "kw_metrics_add_outcomes": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64, C.POINTER(u64), u32, C.POINTER(u64)]),
+        "kw_metrics_record_pass": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64]),
         "kw_batch_pin_host": (ip, [vp, ip]),
         "kw_host_alloc": (ip, [ip, sz, C.POINTER(vp)]),
         "kw_host_free": (None, [vp]),
