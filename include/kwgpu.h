@@ -324,6 +324,25 @@ int kw_debug_sched_rounds(uint64_t ndesc, uint32_t grid, int dynamic, int *round
  * *needed: words; KW_E_NOSPACE when cap is smaller; KW_E_ARG for a batch that is not resident. */
 int kw_debug_last_launches(const kw_batch *b, int64_t *out, size_t cap, size_t *needed);
 
+/* Diagnostic (tests): beside kw_debug_last_launches, the tile kernel each of those launches took, one
+ * word each: 0 the generic kernel of the launch's family set, 1 the production-shape one (DESIGN.md
+ * §5). *needed: words; KW_E_NOSPACE when cap is smaller; KW_E_ARG for a batch that is not resident. */
+int kw_debug_last_kernels(const kw_batch *b, uint32_t *out, size_t cap, size_t *needed);
+
+/* Diagnostic (tests): whether a tile launch of this shape qualifies for a production-shape kernel
+ * (1) or takes the generic one (0) — the launch's own predicate over a launch record made of these
+ * values. feat: the family bits of kw_debug_tile_cost, 16 NFA elements, 32 predecessor ranges by wave
+ * scan; debug: the KW_TILE_DEBUG bits; nchunk: chunks of the launch; ncols / vec4: the first chunk's
+ * verdict columns and whether they are stored 16 bytes at a time; timing: the phase clocks run. */
+int kw_debug_prod_shape(uint32_t feat, int lds_tables, uint32_t debug, uint32_t nchunk, int rows_mode, int prefetch,
+                        uint32_t ncols, int vec4, int timing);
+
+/* Diagnostic (tests): the kernel (as kw_debug_last_kernels) each tile launch of a resident all-pairs
+ * pass would take under the current settings, planned over the batch's host columns (nothing
+ * launched), in launch order. *needed: words; KW_E_NOSPACE when cap is smaller (out untouched). */
+int kw_debug_plan_kernels(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
+                          uint32_t *out, size_t cap, size_t *needed);
+
 /* Diagnostic (tests): the device-row order kw_batch_to_device gives this batch — the light / heavy
  * split (rows with more than 5 containers after the others when they are 1-50 % of
  * a batch of >= 2^18 rows and hold >= 30 % of its containers; KW_SPLIT=0 / 1 never / always) — as a

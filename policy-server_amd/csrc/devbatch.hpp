@@ -149,6 +149,7 @@ struct DeviceBatch {
   uint32_t loaded = 0;        // string columns (bits of Str) whose bytes are resident (kw_validate_host uploads only its pass's)
   uint32_t* sched = nullptr;  // tile counters (zeroed once; each launch leaves them zero)
   std::vector<int64_t> last_launches;  // the last pass's tile launches: (workgroups launched, descriptors, static rounds or -1) each (diagnostic)
+  std::vector<uint32_t> last_kernels;  // the kernel each of those launches took (kernels.hpp tile_kernel_kind)
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   // the last pass's plan as the kernels read it (host copies detect a changed plan)
   TileArgs* d_tiles = nullptr;

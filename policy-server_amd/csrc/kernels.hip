@@ -510,12 +510,34 @@ __device__ inline void prefetch_l2(const void* src, uint32_t bytes, uint8_t* scr
 
 // TIMING: the diagnostics instantiation (EvalArgs::phase) — phase clocks add registers, so the
 // product kernel is compiled without them.
-template <bool LDST, bool TIMING, uint32_t F>
+// PROD: the launch has the production shape (kernels.hpp tile_prod_shape), and the values that
+// shape fixes are constants of the instantiation. The body reads each through one accessor, which is
+// the constant under PROD and the TileArgs field (still loaded where used) otherwise, so each test
+// is stated once, and under PROD it folds away with the code behind it: the ablation arms, the D
+// phase and the chunk loop, the kept class arrays, rows mode, the generic output loops.
+// (Macros, not lambdas: read through a lambda's captured reference the fields lose tp's __restrict__,
+// and the NFA instantiation came out 35 instructions and a VGPR different from its form without the
+// accessors; these expand to the very expressions the generic kernels had.)
+#define KW_SHAPE_DEBUG() (PROD ? 0u : t.debug)
+#define KW_SHAPE_NCHUNK() (PROD ? 1u : t.nchunk)
+#define KW_SHAPE_ROWS_MODE() (PROD ? 0u : t.rows_mode)
+#define KW_SHAPE_PREFETCH() (PROD ? 0u : t.prefetch)
+#define KW_SHAPE_CTR_RANGES() (PROD ? (uint32_t)RNG : t.ctr_ranges)  // fixed by the family set (tile_prod_shape)
+// (not of the shape, but read at four sites a tile: in the plain production kernel loaded once per
+// tile, which added no SGPR spill, readlane or VGPR there; in the kFeatRng one it added a spill and
+// five readlanes, so that one, like the generic kernels, keeps the load at each site)
+#define KW_VW_STRIDE() (PROD && !RNG ? vws : t.vw_stride)
+#define KW_SHAPE_VEC4(ca) (PROD ? 1u : (ca).vec4)
+// G column groups: a power of two that divides the workgroup (each thread keeps one group)
+#define KW_SHAPE_GROUPS_POW2(G) (PROD || (((G) & ((G) - 1u)) == 0 && (G) <= kSlotThreads))
+template <bool LDST, bool TIMING, uint32_t F, bool PROD = false>
 __global__ void __launch_bounds__(kSlotThreads, 1)
     evaluate_tiles_kernel(EvalArgs a, const TileArgs* __restrict__ tp, const TileDesc* __restrict__ desc) {
   // TileArgs lives in device memory: its fields are scalar-loaded where used instead of all being
   // hoisted from the kernarg segment into SGPRs at entry.
   const TileArgs& t = *tp;
+  static_assert(!PROD || (LDST && !TIMING && (F & ~kFeatRng) == (kFeatLbl | kFeatCtr)),
+                "production-shape kernels: LDS tables, no phase clocks, the label / container families");
   // families compiled into this instantiation (TileArgs::feat): images / trusted-repos, labels,
   // container families (pod-privileged, psp-capabilities, psp-apparmor), group columns
   constexpr bool IMG = (F & kFeatImg) != 0, LBL = (F & kFeatLbl) != 0, CTR = (F & kFeatCtr) != 0, GRP = (F & kFeatGrp) != 0;
@@ -630,7 +652,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
     // (a copy through VGPRs waits a latency per loop trip: ~3 trips of 256 x 16 B for C4's 12 KB)
     for (uint32_t s = 0; s < t.nstage; ++s)
       glds_x4((const u32x4*)(a.blob + t.stage_blob[s]), (u32x4*)(lds + t.stage_lds[s]), t.stage_bytes[s] / 16u, tid);
-    for (uint32_t c = 0; c < t.nchunk; ++c)
+    for (uint32_t c = 0; c < KW_SHAPE_NCHUNK(); ++c)
       glds_x4((const u32x4*)t.chunk[c].rec, (u32x4*)(lds + t.chunk[c].o_lds), ((const SlotHdr*)t.chunk[c].rec)->staged / 16u, tid);
   }
   __syncthreads();
@@ -807,7 +829,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
       // their register allocation — C2 -3.3 %, C3 -1.7 % against builds without it — while r05's
       // label / container instantiations are 1.1-1.3 % faster without it and the global-table
       // ones 2 % (r04); profiles/r05_prefetch_code_ab.txt)
-      if (KW_PREFETCH && LDST && IMG && t.prefetch && next < t_hi) {
+      if (KW_PREFETCH && LDST && IMG && KW_SHAPE_PREFETCH() && next < t_hi) {
         const TileDesc& dn = l_desc[cur ^ 1u];
         if (sfield(dn.fits)) {
           const uint64_t q0 = ((uint64_t)sfield(dn.r0hi) << 32) | sfield(dn.r0lo);
@@ -831,8 +853,9 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
         }
       }
     };
+    const uint32_t vws = PROD && !RNG ? t.vw_stride : 0u;  // (KW_VW_STRIDE)
     const uint8_t* cfl = l_cflags + (cb & 3u);  // staged from the dword holding flag cb
-    const bool classify = !(t.debug & 1u);  // diagnostics: skip classification (entities match nothing)
+    const bool classify = !(KW_SHAPE_DEBUG() & 1u);  // diagnostics: skip classification (entities match nothing)
     auto str = [&](int m, uint32_t i, uint32_t* b, uint32_t* e) {
       const uint32_t* so = (const uint32_t*)(lds + t.o_so[m]);
       const uint32_t sa = l_sa[m];
@@ -867,8 +890,8 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
       // bytes with nlv == 2, so lmax >= 128 holds them only while a workgroup is 4 waves)
       static_assert(kSlotThreads == 256u && (kSlotThreads / 64u) * 128u == 128u * 2u * 2u,
                     "the label-pair mailboxes assume 4 waves and a class array of >= 128 labels x 2 x u16");
-      const bool label_pairs = LDST && C.kv && t.kv_lds && nlv == 2u && t.nchunk == 1u && t.lmax >= 128u && classify &&
-                               t.o_sb[S_LV] && !(t.debug & 2048u);
+      const bool label_pairs = LDST && C.kv && t.kv_lds && nlv == 2u && KW_SHAPE_NCHUNK() == 1u && t.lmax >= 128u && classify &&
+                               t.o_sb[S_LV] && !(KW_SHAPE_DEBUG() & 2048u);
       const uint64_t p1_t0 = timing ? clock64() : 0;
       for (uint32_t w = tid; w < e3; w = DYNB ? next_block(0u) * 64u + lane : w + kSlotThreads) {
         seg(w < ek ? SG_P1_LABEL : w < e0 ? SG_P1_CAPSTR : w < e1 ? SG_P1_CTR : w < e2 ? SG_P1_IMAGE : SG_P1_REQ);
@@ -957,13 +980,13 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
           uint16_t* lv = c_lv + i * nlv;
           // chunk 0's failed-constraint slots folded in as the walk yields each value class; the
           // classes themselves are stored only for a pass whose later chunks rederive l_vl (D)
-          const bool keep = t.nchunk > 1u;
+          const bool keep = KW_SHAPE_NCHUNK() > 1u;
           uint64_t vf = 0;
           auto out = [&](uint32_t j, uint32_t c) {
             if (keep) lv[j] = (uint16_t)c;
             if (h0.lbl && c != 0xffffu) vf |= sv0.row(T_FAIL, c);
           };
-          if (k && classify && t.o_sb[S_LV] && !(t.debug & 2048u)) {
+          if (k && classify && t.o_sb[S_LV] && !(KW_SHAPE_DEBUG() & 2048u)) {
             uint32_t b, e;
             str(S_LV, i, &b, &e);
             classify_value<NFA>(C, LDST && t.kv_lds, k, nlv, lds + t.o_sb[S_LV], b, e, out,
@@ -1004,7 +1027,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
             uint32_t b, e;
             str(S_IMG, i, &b, &e);
             classify_image<true, LDST, NFA>(C, il, lds + t.o_sb[S_IMG], b, e, [&](uint32_t j, uint32_t c) { ic[j] = (uint16_t)c; },
-                                 t.debug, NFA ? a.nfa_img + (uint64_t)(cb + i) * nim : nullptr);
+                                 KW_SHAPE_DEBUG(), NFA ? a.nfa_img + (uint64_t)(cb + i) * nim : nullptr);
           } else {
             for (uint32_t j = 0; j < nim; ++j) ic[j] = 0;
           }
@@ -1030,7 +1053,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
     mark(1);
     prefetch_next();
 
-    for (uint32_t ck = 0; ck < t.nchunk; ++ck) {
+    for (uint32_t ck = 0; ck < KW_SHAPE_NCHUNK(); ++ck) {
       const SlotView sv = chunk_view(ck);
       const SlotHdr& SH = *sv.h;
       if (ck > 0) {
@@ -1071,7 +1094,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
       //      (capabilities in list order, trusted-repos reasons in precedence). Request items add
       //      the namespace and mandatory-label slots. Rejected / mutated slots merge with ds_or_b64.
       //      (Sequential form of the same walk: slots.hpp walk_*.)
-      if (!(t.debug & 2u)) {
+      if (!(KW_SHAPE_DEBUG() & 2u)) {
         const uint64_t privany = SH.priv[0] | SH.priv[1] | SH.priv[2] | SH.priv[3];
         const bool trs = IMG && SH.trs != 0;
         const bool ctr_fam = (CTR && (privany | SH.caps | SH.aa) != 0) || trs;
@@ -1108,7 +1131,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
                 if (capv) carry |= or_range(l_vadd, l_cadd[c0] - kab, ka);
               }
               pre = seg_or_scan_excl(own | carry, lane, i, c0) | carry;
-              if (t.debug & 4096u) pre = 0;  // (ablation bit 4096: no predecessor ORs, in every form)
+              if (KW_SHAPE_DEBUG() & 4096u) pre = 0;  // (ablation bit 4096: no predecessor ORs, in every form)
               if (!act || !(l_rf[q] & KW_REQ_HAS_PODSPEC)) continue;
             } else {
             if (i >= n1) continue;
@@ -1119,14 +1142,14 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
             // (a contiguous range of l_vadd); the same for this container
             ka0 = l_cadd[c0] - kab, ka = l_cadd[i] - kab, ka1 = l_cadd[i + 1] - kab;
             own = vset(i);
-            if (t.ctr_ranges) {  // many containers per request: the ranges four loads a round
-              if (!(t.debug & 4096u)) {  // (ablation bit 4096: no predecessor ORs, in both forms)
+            if (KW_SHAPE_CTR_RANGES()) {  // many containers per request: the ranges four loads a round
+              if (!(KW_SHAPE_DEBUG() & 4096u)) {  // (ablation bit 4096: no predecessor ORs, in both forms)
                 pre = (CTR ? or_range(l_vc, c0, i) : 0ull) | (trs ? or_range(l_vtr, c0, i) : 0ull);
                 if (capv) pre |= or_range(l_vadd, ka0, ka);
               }
               if (capv) own |= or_range(l_vadd, ka, ka1);
             } else {
-              if (!(t.debug & 4096u)) {
+              if (!(KW_SHAPE_DEBUG() & 4096u)) {
                 for (uint32_t j = c0; j < i; ++j) pre |= vset(j);
                 if (capv)
                   for (uint32_t k = ka0; k < ka; ++k) pre |= l_vadd[k];
@@ -1137,8 +1160,8 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
             }
             const uint64_t nv = own & ~pre;
             const uint32_t ci = i - c0;
-            uint32_t* vw = l_vw + q * t.vw_stride;
-            if (nv && !(t.debug & 16384u)) {
+            uint32_t* vw = l_vw + q * KW_VW_STRIDE();
+            if (nv && !(KW_SHAPE_DEBUG() & 16384u)) {
               ViolSink vs{vw, nullptr};
               if (CTR) {
                 vs.put(nv & privany, KW_R_PRIVILEGED, ci);
@@ -1164,7 +1187,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
               }
               atomicOr((unsigned long long*)&l_rej[q], (unsigned long long)nv);
             }
-            if (CTR && SH.caps && !(t.debug & 8192u)) {  // mutation: required drops missing, default adds neither added nor dropped
+            if (CTR && SH.caps && !(KW_SHAPE_DEBUG() & 8192u)) {  // mutation: required drops missing, default adds neither added nor dropped
               uint64_t addm = 0, dropm = 0;
               for (uint32_t k = ka; k < ka1; ++k) addm |= bit_of(sv.capmb(c_add[k]));
               for (uint32_t k = l_cdrop[i] - kdb, k1 = l_cdrop[i + 1] - kdb; k < k1; ++k) dropm |= bit_of(sv.capmb(c_drop[k]));
@@ -1181,10 +1204,10 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
             uint64_t pre = 0;
             for (uint32_t j = l0; j < i; ++j) pre |= l_vl[j];
             const uint64_t nv = v & ~pre;
-            if (!nv || (t.debug & 16384u)) continue;
+            if (!nv || (KW_SHAPE_DEBUG() & 16384u)) continue;
             const uint64_t den = sv.row(T_DENY, c_lk[i]);
             const uint32_t li = i - l0;
-            ViolSink vs{l_vw + q * t.vw_stride, nullptr};
+            ViolSink vs{l_vw + q * KW_VW_STRIDE(), nullptr};
             vs.put(nv & den, KW_R_LABEL_DENIED, li);
             vs.put(nv & ~den, KW_R_LABEL_CONSTRAINT, li);
             atomicOr((unsigned long long*)&l_rej[q], (unsigned long long)nv);
@@ -1192,14 +1215,14 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
             const uint32_t i = w - (DYNB ? f0 : f1);
             if (i >= nr) continue;
             const uint32_t rf = l_rf[i];
-            ViolSink vs{l_vw + i * t.vw_stride, nullptr};
+            ViolSink vs{l_vw + i * KW_VW_STRIDE(), nullptr};
             uint64_t rej = 0;
             if (SH.ns) {
               const uint64_t ok = (rf & KW_REQ_HAS_NAMESPACE) ? sv.row(T_NSOK, c_ns[i]) : 0ull;
               rej = SH.ns & ~ok;
               vs.put(rej, KW_R_NAMESPACE, 0);
             }
-            if (LBL && SH.lbl && SH.mand_union && !(t.debug & 1024u)) {
+            if (LBL && SH.lbl && SH.mand_union && !(KW_SHAPE_DEBUG() & 1024u)) {
               uint64_t present = 0, lrej = 0;
               for (uint32_t l = l_loff[i] - lb, l1 = l_loff[i + 1] - lb; l < l1; ++l) {
                 present |= bit_of(sv.lkmb(c_lk[l]));
@@ -1252,7 +1275,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
       //      column records from LDS (group / constant columns from the record's global copy).
       //      Rows mode: one word per request, its own column.
       const uint64_t p3_t0 = timing ? clock64() : 0;
-      if (!(t.debug & 4u)) {
+      if (!(KW_SHAPE_DEBUG() & 4u)) {
         const ChunkArgs& CA = t.chunk[ck];
         const uint64_t init = CA.init;
         const ColInfo* cols = (const ColInfo*)(CA.rec + SH.o_cols);
@@ -1269,13 +1292,13 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
           if (cols[j].wide != ~0u && KW_REASON(w) == KW_R_GROUP) a.wide_groups[(r0 + rr) * a.nwide + cols[j].wide] = wide;
           return w;
         };
-        if (t.rows_mode) {
+        if (KW_SHAPE_ROWS_MODE()) {
           for (uint32_t rr = tid; rr < nr; rr += kSlotThreads) {
             const uint32_t rc = a.rowcol[r0 + rr];
             if ((rc >> 16) != ck) continue;
             out[r0 + rr] = l_byp[rr] ? kBypassWord : word(rr, rc & 0xffffu);
           }
-        } else if (CA.vec4) {
+        } else if (KW_SHAPE_VEC4(CA)) {
           const uint32_t* cs = (const uint32_t*)(sv.base + SH.o_csoa);
           const uint32_t cs_n = (ncols + 3u) & ~3u;
           const uint32_t G = ncols >> 2;
@@ -1309,7 +1332,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
             const u32x4 nv4 = {wv.x, wv.y, wv.z, wv.w};
             __builtin_nontemporal_store(nv4, (u32x4*)dst);  // streamed once
           };
-          if ((G & (G - 1u)) == 0 && G <= kSlotThreads) {
+          if (KW_SHAPE_GROUPS_POW2(G)) {
             // G a power of two dividing the workgroup: each thread keeps one column group for every
             // request it writes, so the column data is loaded once and no division is needed
             const uint32_t lg = (uint32_t)__builtin_ctz(G), g = tid & (G - 1u), step = kSlotThreads >> lg;
@@ -1337,13 +1360,36 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
                 wd[k] = pl ? 1u : 0u;
                 muw[k] = pl ? muc[k] : okc[k];
               }
+              // PROD: the row's seven LDS reads from 32-bit LDS addresses, formed once before the
+              // loop (as kv_walk forms its own). Through the pointers of the opaque region offsets
+              // every read re-adds the LDS base inside the loop: seven v_add_u32 v, 0, v a row.
+              typedef const __attribute__((address_space(3))) uint8_t* lds8;
+              auto lds_addr = [](const void* p) -> uint32_t {
+                uint32_t a = (uint32_t)(uintptr_t)(lds8)(const uint8_t*)p;
+                asm("" : "+v"(a));
+                return a;
+              };
+              const uint32_t a_rej = PROD ? lds_addr(l_rej) : 0u, a_mut = PROD ? lds_addr(l_mut) : 0u,
+                             a_byp = PROD ? lds_addr(l_byp) : 0u, a_vw = PROD ? lds_addr(l_vw) : 0u;
               for (uint32_t rr = tid >> lg; rr < nr; rr += step, dst += dstep) {
-                const uint2 rj = *(const uint2*)&l_rej[rr], mu = *(const uint2*)&l_mut[rr];
-                const uint32_t byp = l_byp[rr];
-                const uint32_t* vw = l_vw + rr * t.vw_stride;
-                uint32_t av[4], wk[4];
+                uint2 rj, mu;
+                uint32_t byp, av[4], wk[4];
+                if constexpr (PROD) {
+                  const uint64_t rj64 = *(const __attribute__((address_space(3))) uint64_t*)(uintptr_t)(a_rej + rr * 8u);
+                  const uint64_t mu64 = *(const __attribute__((address_space(3))) uint64_t*)(uintptr_t)(a_mut + rr * 8u);
+                  rj = make_uint2((uint32_t)rj64, (uint32_t)(rj64 >> 32));
+                  mu = make_uint2((uint32_t)mu64, (uint32_t)(mu64 >> 32));
+                  byp = *(lds8)(uintptr_t)(a_byp + rr);
+                  const uint32_t vwa = a_vw + rr * KW_VW_STRIDE() * 4u;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) av[k] = vw[cs[k]];
+                  for (int k = 0; k < 4; ++k) av[k] = *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)(vwa + cs[k] * 4u);
+                } else {
+                  rj = *(const uint2*)&l_rej[rr], mu = *(const uint2*)&l_mut[rr];
+                  byp = l_byp[rr];
+                  const uint32_t* vw = l_vw + rr * t.vw_stride;
+#pragma unroll
+                  for (int k = 0; k < 4; ++k) av[k] = vw[cs[k]];
+                }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                   const uint32_t rb = (uint32_t)__builtin_amdgcn_sbfe((int)(hi[k] ? rj.y : rj.x), bs[k], wd[k]);
@@ -1395,7 +1441,7 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
         }
       }
       if (timing) sg_add(SG_P3_BUSY, clock64() - p3_t0);
-      if (ck + 1 < t.nchunk) {
+      if (ck + 1 < KW_SHAPE_NCHUNK()) {
         if (DYNB && tid == 0) l_nx[3] = 0;  // the next chunk's P2 block counter
         lds_barrier();  // the next chunk rewrites the violation sets and words
         mark(4);
@@ -1435,6 +1481,15 @@ __global__ void __launch_bounds__(kSlotThreads, 1)
   (void)lane;
   (void)wave;
 }
+
+#undef KW_SHAPE_DEBUG
+#undef KW_SHAPE_NCHUNK
+#undef KW_SHAPE_ROWS_MODE
+#undef KW_SHAPE_PREFETCH
+#undef KW_SHAPE_CTR_RANGES
+#undef KW_SHAPE_VEC4
+#undef KW_VW_STRIDE
+#undef KW_SHAPE_GROUPS_POW2
 
 // ------------------------------------------------------------------------------------------
 // Overflow: requests whose entity counts or string bytes exceed the tile capacities even alone
@@ -1772,7 +1827,12 @@ template <bool LDST, uint32_t... Fs>
 constexpr std::array<const void*, sizeof...(Fs)> tile_fns() {
   return {(const void*)evaluate_tiles_kernel<LDST, false, Fs>...};
 }
-const void* tile_fn(bool ldst, bool timing, uint32_t feat) {
+// prod: the launch has the production shape (tile_prod_shape, which admits only the two family sets
+// below, LDS tables and no timing), and takes the instantiation with that shape compiled in.
+const void* tile_fn(bool ldst, bool timing, uint32_t feat, bool prod) {
+  if (prod)
+    return (feat & kFeatRng) ? (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr | kFeatRng, true>
+                             : (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr, true>;
   static const auto g = tile_fns<false, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>();
   static const auto l = tile_fns<true, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>();
   if (feat & kFeatNfa)  // the one instantiation with NFA elements: every family (timing runs it too)
@@ -1798,10 +1858,14 @@ hipError_t ensure_attrs() {
   std::call_once(g_attr_once[dev], [dev] {
     // allow > 64 KB of dynamic LDS per workgroup (gfx950: 160 KB per CU)
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 70; ++k) {  // (LDS tables, timing, families; the two NFA instantiations; the scan one at k = 69)
-      const uint32_t feat = k < 64 ? (uint32_t)(k >> 2) & kFeatAll : k < 68 ? (kFeatAll | kFeatNfa) : (kFeatLbl | kFeatCtr | kFeatRng);
-      const hipError_t ek =
-          hipFuncSetAttribute(tile_fn(k & 1, (k & 2) != 0, feat), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // (LDS tables, timing, families; the two NFA instantiations; the scan one at k = 69; the two production-shape ones)
+    for (int k = 0; k < 72; ++k) {
+      const uint32_t feat = k < 64   ? (uint32_t)(k >> 2) & kFeatAll
+                            : k < 68 ? (kFeatAll | kFeatNfa)
+                                     : (kFeatLbl | kFeatCtr | (k == 70 ? 0u : kFeatRng));
+      const bool prod = k >= 70;
+      const hipError_t ek = hipFuncSetAttribute(tile_fn(prod || (k & 1), !prod && (k & 2) != 0, feat, prod),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e == hipSuccess) e = ek;
     }
     g_attr_err[dev] = e;
@@ -1809,6 +1873,8 @@ hipError_t ensure_attrs() {
   return g_attr_err[dev];
 }
 }  // namespace
+
+uint32_t tile_kernel_kind(const TileArgs& t, bool timing) { return tile_prod_shape(t, timing) ? kTileKernelProd : kTileKernelGeneric; }
 
 uint32_t tile_launch_grid(const TileArgs& t, bool timing, uint32_t grid, bool print) {
   // The grid is persistent (tiles strided by gridDim.x), so it must be co-resident: a workgroup
@@ -1818,10 +1884,12 @@ uint32_t tile_launch_grid(const TileArgs& t, bool timing, uint32_t grid, bool pr
   thread_local int c_dev = -1, c_ncu = 0, c_occ = 0;
   thread_local uint64_t c_key = ~0ull;
   int dev = 0;
-  const uint64_t key = ((uint64_t)t.lds_bytes << 8) | ((uint64_t)tile_feat(t) << 2) | (timing ? 2u : 0u) | (t.lds_tables ? 1u : 0u);
+  const bool prod = tile_kernel_kind(t, timing) == kTileKernelProd;
+  const uint64_t key = ((uint64_t)t.lds_bytes << 9) | (prod ? 256u : 0u) | ((uint64_t)tile_feat(t) << 2) | (timing ? 2u : 0u) |
+                       (t.lds_tables ? 1u : 0u);
   if (hipGetDevice(&dev) == hipSuccess && (dev != c_dev || key != c_key)) {
     int ncu = 0, occ = 0;
-    const void* fn = tile_fn(t.lds_tables != 0, timing, tile_feat(t));
+    const void* fn = tile_fn(t.lds_tables != 0, timing, tile_feat(t), prod);
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kSlotThreads, t.lds_bytes) != hipSuccess)
       ncu = occ = 0;
@@ -1844,7 +1912,8 @@ hipError_t launch_evaluate_tiles(const EvalArgs& a, const TileArgs& t, const Til
   if (hipError_t e = ensure_attrs(); e != hipSuccess) return e;
   grid = tile_launch_grid(t, a.phase != nullptr, grid, /*print=*/true);  // (an already clamped grid stays as it is)
   using TileFn = void (*)(EvalArgs, const TileArgs*, const TileDesc*);
-  const TileFn fn = (TileFn)tile_fn(t.lds_tables != 0, a.phase != nullptr, tile_feat(t));
+  const TileFn fn = (TileFn)tile_fn(t.lds_tables != 0, a.phase != nullptr, tile_feat(t),
+                                    tile_kernel_kind(t, a.phase != nullptr) == kTileKernelProd);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(kSlotThreads), t.lds_bytes, s, a, d_t, d_desc);
   return hipGetLastError();
 }

@@ -198,7 +198,27 @@ struct TileArgs {
                   // 8192 skip capability mutations (P2), 16384 skip container / label violation words (P2),
                   // 32768 / 65536 skip the image DFA chains / literal lookups (P1)
   uint32_t lds_bytes;
+  uint32_t generic;  // KW_TILE_GENERIC: the launch takes the generic kernel whatever its shape (host side only)
 };
+
+// The production shape of a launch: the ordinary all-pairs pass of a label / container policy set,
+// whose tile kernel is compiled with these values as constants (evaluate_tiles_kernel's PROD, the
+// shape_* accessors in kernels.hip): no ablation bit, one chunk, all pairs, no L2 prefetch, 16-byte
+// verdict stores with a power-of-two number of column groups that divides the workgroup, tables in
+// LDS, no NFA element, and the family set one of the two that have such a kernel (with kFeatRng
+// exactly where the tiles take predecessor ranges). timing: the pass runs the phase clocks
+// (EvalArgs::phase), which stay on the generic kernel. The launch (tile_kernel_kind) and the tests
+// (kw_debug_prod_shape) decide by this one function.
+inline bool tile_prod_shape(const TileArgs& t, bool timing) {
+  const uint32_t feat = t.feat & (kFeatAll | kFeatNfa | kFeatRng);
+  if (feat != (kFeatLbl | kFeatCtr) && feat != (kFeatLbl | kFeatCtr | kFeatRng)) return false;
+  if ((t.ctr_ranges != 0) != ((feat & kFeatRng) != 0)) return false;
+  if (timing || t.generic || t.debug != 0 || !t.lds_tables) return false;
+  if (t.nchunk != 1 || t.rows_mode || t.prefetch) return false;
+  const ChunkArgs& c = t.chunk[0];
+  const uint32_t G = c.ncols / 4u;
+  return c.vec4 && c.ncols % 4u == 0 && G >= 1 && (G & (G - 1u)) == 0 && G <= kSlotThreads;
+}
 
 // Per-tile geometry, precomputed on the host from the batch's offsets (one s_load burst per tile
 // instead of a chain of dependent global loads): entity ranges, the 16-B aligned byte range of each
@@ -305,6 +325,11 @@ void build_copy_jobs(TileArgs* T, const void* const cols[6]);
 // Needs the launch's device current; with no device the grid comes back as it is.
 // print: with KW_TILE_DEBUG & 256, the [kw tile] line of the launch.
 uint32_t tile_launch_grid(const TileArgs& t, bool timing, uint32_t grid, bool print = false);
+// The kernel a launch of `t` takes: the production-shape instantiation where tile_prod_shape holds,
+// else the generic one of its family set. launch_evaluate_tiles and tile_launch_grid choose by it,
+// and a pass reports it per launch (kw_debug_last_kernels).
+constexpr uint32_t kTileKernelGeneric = 0, kTileKernelProd = 1;
+uint32_t tile_kernel_kind(const TileArgs& t, bool timing);
 
 // One launch of the tile kernel over chunks t.chunk[0..nchunk). t: host copy (launch geometry);
 // d_t: the same TileArgs resident in device memory (read by the kernel).

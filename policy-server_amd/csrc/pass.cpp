@@ -478,6 +478,7 @@ static int run_pass(kw_batch* kb, PassPlan& plan, bool timed, hipStream_t s) {
   // own descriptors; the overflow kernels after the last region, over the one overflow list
   const size_t nl = plan.launches.size();
   D.last_launches.clear();
+  D.last_kernels.clear();
   for (size_t l = 0; l < plan.tiles.size(); ++l) {
     const size_t k = l / nl;
     if (phases) HIPCHK(hipMemsetAsync(d_phase, 0, phase_bytes, s));
@@ -492,6 +493,7 @@ static int run_pass(kw_batch* kb, PassPlan& plan, bool timed, hipStream_t s) {
     if (S < 0) Ak.sched = nullptr;
     else Ak.sched_static = (uint32_t)S;
     for (int64_t v : {(int64_t)grid, (int64_t)Ak.ndesc, (int64_t)S}) D.last_launches.push_back(v);
+    D.last_kernels.push_back(tile_kernel_kind(plan.tiles[l], phases));
     HIPCHK(launch_evaluate_tiles(Ak, plan.tiles[l], D.d_tiles + l, D.desc + D.reg_desc[k], grid, s));
     if (phases) {
       std::vector<uint64_t> ph((size_t)grid * kPhaseWords);

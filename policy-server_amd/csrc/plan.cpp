@@ -700,6 +700,7 @@ void share_fields(TileArgs& T, const DevHeader* H, const PassNeeds& N, const Tab
     T.kv_lds = 0;
   }
   T.debug = debug;  // phase ablation (diagnostics)
+  T.generic = PlanKnobs::on<KW_TILE_GENERIC>() ? 1u : 0u;  // (kernels.hpp tile_prod_shape)
   const void* const cols[6] = {D.req_flags, D.ctr_off, D.lbl_off, D.ctr_flags, D.capadd_off, D.capdrop_off};
   build_copy_jobs(&T, cols);
 }

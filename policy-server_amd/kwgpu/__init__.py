@@ -18,6 +18,8 @@ from ._native import KwSoa, KwTiming  # noqa: F401
 
 PROTECT, MONITOR = N.KW_MODE_PROTECT, N.KW_MODE_MONITOR
 VALIDATE, AUDIT = N.KW_ORIGIN_VALIDATE, N.KW_ORIGIN_AUDIT
+# the tile kernel a launch took (Batch.debug_last_kernels): the generic one, or the production-shape one
+KERNEL_GENERIC, KERNEL_PROD = 0, 1
 
 
 class RequestOrigin:
@@ -728,6 +730,32 @@ class Batch:
         out = (C.c_int64 * need.value)()
         raise_for(self._L.kw_debug_last_launches(self._h, out, need.value, C.byref(need)), "kw_debug_last_launches failed")
         return [tuple(out[i:i + 3]) for i in range(0, need.value, 3)]
+
+    def debug_last_kernels(self):
+        """Diagnostic (kw_debug_last_kernels): beside debug_last_launches, the tile kernel each
+        launch of the batch's last resident pass took (KERNEL_GENERIC / KERNEL_PROD)."""
+        need = C.c_size_t()
+        rc = self._L.kw_debug_last_kernels(self._h, None, 0, C.byref(need))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_debug_last_kernels failed")
+            return []
+        out = (C.c_uint32 * need.value)()
+        raise_for(self._L.kw_debug_last_kernels(self._h, out, need.value, C.byref(need)), "kw_debug_last_kernels failed")
+        return list(out)
+
+    def debug_plan_kernels(self, env, policies, origin=VALIDATE):
+        """Diagnostic (kw_debug_plan_kernels): the tile kernel each launch of a resident all-pairs
+        pass would take under the current settings, planned on the host."""
+        arr = env._array(policies)
+        need = C.c_size_t()
+        rc = self._L.kw_debug_plan_kernels(env._h, self._h, arr, len(policies), origin, None, 0, C.byref(need))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_debug_plan_kernels failed")
+            return []
+        out = (C.c_uint32 * need.value)()
+        raise_for(self._L.kw_debug_plan_kernels(env._h, self._h, arr, len(policies), origin, out, need.value, C.byref(need)),
+                  "kw_debug_plan_kernels failed")
+        return list(out)
 
     def debug_reorder(self):
         """Diagnostic (kw_debug_reorder): the device-row order kw_batch_to_device gives this batch,

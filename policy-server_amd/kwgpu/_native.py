@@ -113,6 +113,7 @@ EXPORTS = [
     "kw_env_policy_initialization_error", "kw_env_validate_settings", "kw_pattern_match", "kw_pattern_match_many", "kw_env_pattern_count",
     "kw_env_pattern", "kw_env_classify", "kw_batch_wide_arg", "kw_batch_group_causes", "kw_debug_plan", "kw_debug_copy_jobs", "kw_debug_reorder",
     "kw_debug_tile_descs", "kw_debug_tile_cost", "kw_debug_tile_slot", "kw_debug_sched_tail", "kw_debug_sched_rounds", "kw_debug_last_launches",
+    "kw_debug_last_kernels", "kw_debug_prod_shape", "kw_debug_plan_kernels",
     "kw_batch_from_json", "kw_batch_from_soa", "kw_batch_view", "kw_batch_to_device", "kw_batch_to_device_async",
     "kw_stream_create", "kw_stream_destroy", "kw_validate_host", "kw_validate_host_packed", "kw_packed_word",
     "kw_packed_unpack", "kw_debug_pack_words", "kw_batch_summary", "kw_validate_host_summary", "kw_batch_verdict_rows",
@@ -178,6 +179,9 @@ def lib():
         "kw_debug_sched_tail": (ip, [u64, u32, u32, u32, C.POINTER(u64)]),
         "kw_debug_sched_rounds": (ip, [u64, u32, ip, C.POINTER(ip)]),
         "kw_debug_last_launches": (ip, [vp, C.POINTER(C.c_int64), sz, C.POINTER(sz)]),
+        "kw_debug_last_kernels": (ip, [vp, C.POINTER(u32), sz, C.POINTER(sz)]),
+        "kw_debug_prod_shape": (ip, [u32, ip, u32, u32, ip, ip, u32, ip, ip]),
+        "kw_debug_plan_kernels": (ip, [vp, vp, C.POINTER(i32), u32, ip, C.POINTER(u32), sz, C.POINTER(sz)]),
         "kw_debug_reorder": (ip, [vp, C.POINTER(u64), sz, C.POINTER(u64), C.POINTER(vp)]),
         "kw_batch_from_json": (ip, [C.POINTER(cp), C.POINTER(sz), sz, ip, C.POINTER(vp), C.POINTER(C.c_int64), cp, sz]),
         "kw_batch_from_soa": (ip, [C.POINTER(KwSoa), C.POINTER(vp)]),
