@@ -526,6 +526,77 @@ int kw_debug_outcome_words(const uint32_t *words, uint64_t rows, uint32_t npol, 
  * The batch keeps the result: a second call does not rebuild it. */
 int kw_batch_attribute_groups(const kw_batch *b, uint32_t *row_group, uint64_t *first_row, size_t cap,
                               uint32_t *ngroups);
+/* The violation digest of a pass of rows x npol: its findings grouped by cause, for callers that want
+ * to know what is wrong and how often before they format a single message (an audit scan over many
+ * Pods). A finding is a pair (row, column) whose word has KW_REASON != 0. Its key is what the message
+ * of the reason quotes from the request or the settings, apart from the container's name:
+ *   KW_R_PRIVILEGED                      nothing
+ *   KW_R_NAMESPACE                       the row's ns string
+ *   KW_R_REG_NOT_ALLOWED..KW_R_IMG_REJECTED  the ctr_image string, as it stands in the column, of
+ *                                        container ctr_off[row] + ARG
+ *   KW_R_CAP_NOT_ALLOWED                 the cap_add string at capadd_off[ctr_off[row]] + ARG
+ *   KW_R_APPARMOR                        ctr_apparmor of container ctr_off[row] + ARG
+ *   KW_R_LABEL_DENIED                    lbl_key of label lbl_off[row] + ARG
+ *   KW_R_LABEL_CONSTRAINT                that label's key and value, two strings whose lengths are part
+ *                                        of the key: ("ab", "c") and ("a", "bc") differ
+ *   any other reason (12-15, and values no product word has, such as the KW_POISON_VERDICTS
+ *   sentinel's)                          the 16-bit ARG as a number
+ * (an entity index the column does not hold, which no product word names, reads as ""). Two findings
+ * are one group when their column, their reason, their KW_F_ALLOWED bit (a finding that was let
+ * through does not mix with one that rejected) and their key, byte for byte, are equal. A finding
+ * whose ARG is KW_ARG_WIDE belongs to no group when its reason takes an entity index (1, 3-11) or is
+ * KW_R_GROUP: it is listed in `wide` as the pair index row * npol + col, for kw_batch_wide_arg /
+ * kw_batch_group_causes. All arrays caller-owned:
+ *   recs      kw_digest_rec[cap]: the groups ordered by (col, reason, first_row). first_row is the
+ *             group's lowest batch row, word the verdict word of (first_row, col), so
+ *             kw_format_response(row = first_row, ..., word) gives a representative message; count the
+ *             group's findings. Two groups of one column never share a first_row: the order is total.
+ *   wide      u64[wide_cap]: the wide findings' pair indices, ascending.
+ *   n, nwide, findings (outputs): the groups, the wide findings, and all findings of the pass, the
+ *             wide ones included: the counts of recs add up to findings - nwide.
+ * When cap or wide_cap is too small: KW_E_NOSPACE with the exact n and nwide, the arrays' contents
+ * then unspecified (as kw_validate_host_packed treats exc_cap). The same input gives the same bytes.
+ * No reference counterpart (an output form of a pass, as the packed and the summary forms). */
+typedef struct kw_digest_rec {
+  uint32_t col;
+  uint32_t word;
+  uint64_t first_row;
+  uint64_t count;
+} kw_digest_rec;
+typedef struct kw_digest {
+  kw_digest_rec *recs;
+  size_t cap;
+  size_t n;
+  uint64_t *wide;
+  size_t wide_cap;
+  size_t nwide;
+  uint64_t findings;
+} kw_digest;
+/* The digest of the batch's last all-pairs device pass (kw_validate_batch or a bulk pass), reduced on
+ * the device over the words where they lie and the string columns the pass read: the findings are
+ * hashed into a table of KW_DIGEST_TABLE bytes (default 64 MB), a second launch compares every
+ * finding's key bytes with its group's representative so that the result is exact whatever the hash
+ * does, and only the records and the wide list come back. Synchronises with the pass's stream as
+ * kw_batch_summary does. A group never spans columns: a pass with more groups than the table takes
+ * is reduced in column ranges, halved until each fits; KW_E_NOSPACE with n = 0 only when the groups
+ * of a single column do not fit (more than half of the table's 24-byte slots, a power of two, or, with
+ * KW_DIGEST_HASH_BITS lowered, more colliding findings than the leftover list of 65536 holds).
+ * KW_E_ARG after kw_validate_rows (its one column has a policy per row), for a batch without a pass,
+ * for rows >= 2^32 and when a finding's key column is not resident (a bulk pass uploads only the
+ * columns it reads, which are the ones its reasons quote). A pass without findings gives n = 0. */
+int kw_batch_digest(kw_batch *b, kw_digest *out);
+/* Diagnostic (tests, documents): the same digest from full words [rows][npol] (rows <= the batch's)
+ * and the host batch, by the reference reducer: an ordered map over the exact keys, no hashing. */
+int kw_debug_digest_words(const kw_batch *b, const uint32_t *words, uint64_t rows, uint32_t npol, kw_digest *out);
+/* The key bytes of the finding `word` at batch row `row`, host only: *need bytes (written while they
+ * fit in cap, else KW_E_NOSPACE). For KW_R_LABEL_CONSTRAINT the label's key is followed by its value
+ * and *split is the key's length; otherwise *split = *need. A numeric or empty key has need 0. */
+int kw_batch_finding_key(const kw_batch *b, uint64_t row, uint32_t word, char *buf, size_t cap, size_t *need,
+                         size_t *split);
+/* Diagnostic (tests): what the batch's last kw_batch_digest did. out[0..4): the column ranges that ran
+ * to the end, the findings the verify launch handed to the host (leftovers), the table's slots, and
+ * the ranges that were cut. KW_E_ARG for a batch that was never digested. */
+int kw_debug_digest_stats(const kw_batch *b, uint64_t *out);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes

@@ -205,6 +205,9 @@ struct DeviceBatch {
   uint32_t last_nwide = 0, last_wide_cap = 0;
   bool last_rows_mode = false;
   std::vector<int32_t> last_wide_policy;
+  // the last kw_batch_digest (kw_debug_digest_stats): ranges run, leftovers, table slots, ranges cut
+  bool digest_ran = false;
+  uint64_t digest_stats[4] = {0, 0, 0, 0};
   // tile capacities of this batch (plan_pass), per tile height tried
   struct RowsPlan {
     uint32_t rows = 0;

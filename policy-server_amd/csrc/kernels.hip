@@ -2307,6 +2307,235 @@ hipError_t launch_outcomes(const OutcomeArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- violation digest (kernels.hpp DigestArgs, digest.hpp) ---------------------------------------
+
+constexpr uint64_t kDigestNone = ~0ull;
+
+__device__ inline uint64_t digest_load(const uint64_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void digest_overflow(const DigestArgs& a) {
+  __hip_atomic_store(&a.head->overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The slot that holds `tag`, claimed when none does yet (claim); kDigestNone when the tag is absent or
+// the probe gives up (which, claiming, marks the range as overflowed: the host cuts it).
+__device__ inline uint64_t digest_slot(const DigestArgs& a, uint64_t tag, bool claim) {
+  const uint64_t mask = a.nslots - 1u;
+  uint64_t i = tag & mask;
+  for (uint32_t probe = 0; probe < kDigestProbe; ++probe, i = (i + 1u) & mask) {
+    // a range that has overflowed is cut and counted again: nothing more goes into its table, whose
+    // probes would grow to kDigestProbe slots each past the load factor. Looked at on a long probe
+    // only: one address read by every finding cost C4's count launch 19 ms (profiles/r14_digest.txt).
+    if (claim && probe == 8u && __hip_atomic_load(&a.head->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return kDigestNone;
+    uint64_t* tp = &a.table[i].tag;
+    uint64_t t = digest_load(tp);
+    if (t == 0u) {
+      if (!claim) return kDigestNone;
+      uint64_t expect = 0;
+      if (__hip_atomic_compare_exchange_strong(tp, &expect, tag, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        const uint64_t n = __hip_atomic_fetch_add(&a.head->nclaimed, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n >= digest_max_groups(a.nslots)) digest_overflow(a);
+        return i;
+      }
+      t = expect;
+    }
+    if (t == tag) return i;
+  }
+  if (claim) digest_overflow(a);
+  return kDigestNone;
+}
+
+// A lane's run of findings of one tag into the tag's slot.
+__device__ inline void digest_flush(const DigestArgs& a, uint64_t tag, uint64_t cnt, uint64_t rep) {
+  if (!cnt) return;
+  const uint64_t i = digest_slot(a, tag, true);
+  if (i == kDigestNone) return;
+  __hip_atomic_fetch_add(&a.table[i].count, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (digest_load(&a.table[i].rep) < rep)  // (the value only grows: a load that cannot win saves the atomic)
+    __hip_atomic_fetch_max(&a.table[i].rep, rep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The sum of v over the wave, in lane 0.
+__device__ inline uint64_t digest_wave_sum(uint64_t v) {
+  for (int d = 32; d > 0; d >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)v, d), hi = (uint32_t)__shfl_down((int)(uint32_t)(v >> 32), d);
+    v += ((uint64_t)hi << 32) | lo;
+  }
+  return v;
+}
+
+// The string columns of `need` that are not resident (0: all are); a finding that lacks one is left out
+// and the call answers KW_E_ARG.
+__device__ inline uint32_t digest_lacks(const DigestArgs& a, uint32_t word) {
+  const uint32_t lack = digest_need(digest_kind(KW_REASON(word))) & ~a.loaded;
+  if (lack) __hip_atomic_fetch_or(&a.head->missing, lack, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return lack;
+}
+
+// A lane keeps one column for the whole launch, and a column's busy groups are few (a numeric key has a
+// handful of values, a common capability many rows), so each lane holds kDigestHold runs of findings by
+// tag in registers and only an evicted run, the one with the fewest findings, goes to the table: a busy
+// group costs one add per eviction instead of one per finding (C4 1M: the count launch 21.3 -> 10.3 ms,
+// profiles/r14_digest.txt).
+constexpr uint32_t kDigestHold = 4;
+
+__global__ void __launch_bounds__(256) digest_count_kernel(DigestArgs a, PackGeom p) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, grp = a.c0 / 64u + blockIdx.y;
+  const uint64_t unit = digest_unit_rows(p), stride = (uint64_t)kDigestWaves * gridDim.x * unit;
+  uint64_t h_tag[kDigestHold], h_cnt[kDigestHold], h_rep[kDigestHold], n_find = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kDigestHold; ++k) h_tag[k] = h_cnt[k] = h_rep[k] = 0;
+  for (uint64_t row0 = ((uint64_t)blockIdx.x * kDigestWaves + wave) * unit; row0 < a.cols.rows; row0 += stride) {  // wave-uniform
+    // a range that has overflowed is cut and counted again: the rest of this launch is not needed
+    if (__hip_atomic_load(&a.head->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;  // (one address: wave-uniform)
+    uint32_t x[kDigestRounds];
+#pragma unroll
+    for (uint32_t t = 0; t < kDigestRounds; ++t) {
+      const DigestLane L = digest_lane(p, a.cols.rows, a.c0, a.c1, grp, row0, t, lane);
+      x[t] = L.on ? __builtin_nontemporal_load(a.words + L.row * a.npol + L.col) : 0u;  // (0: no finding)
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < kDigestRounds; ++t) {
+      const uint32_t v = x[t];
+      if (!digest_finding(v)) continue;
+      ++n_find;
+      const DigestLane L = digest_lane(p, a.cols.rows, a.c0, a.c1, grp, row0, t, lane);
+      if (digest_wide(v)) {
+        const uint64_t n = __hip_atomic_fetch_add(&a.head->nwide, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n < a.wide_cap) a.wide[n] = L.row * a.npol + L.col;
+        continue;
+      }
+      if (digest_lacks(a, v)) continue;
+      const uint64_t tag = digest_tag(digest_hash(L.col, digest_class(v), digest_key(a.cols, L.row, v)), a.hash_bits);
+      const uint64_t rep = digest_rep(a.d2b ? a.d2b[L.row] : L.row, L.col);
+      bool hit = false;
+      uint32_t victim = 0;
+      uint64_t least = ~0ull;
+#pragma unroll
+      for (uint32_t k = 0; k < kDigestHold; ++k) {
+        if (!hit && h_tag[k] == tag) {
+          ++h_cnt[k];
+          h_rep[k] = rep > h_rep[k] ? rep : h_rep[k];
+          hit = true;
+        }
+        if (h_cnt[k] < least) {  // (a free entry has count 0: taken first)
+          least = h_cnt[k];
+          victim = k;
+        }
+      }
+      if (hit) continue;
+#pragma unroll
+      for (uint32_t k = 0; k < kDigestHold; ++k) {
+        if (k != victim) continue;
+        digest_flush(a, h_tag[k], h_cnt[k], h_rep[k]);
+        h_tag[k] = tag;
+        h_cnt[k] = 1;
+        h_rep[k] = rep;
+      }
+    }
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < kDigestHold; ++k) digest_flush(a, h_tag[k], h_cnt[k], h_rep[k]);
+  n_find = digest_wave_sum(n_find);
+  if (lane == 0u && n_find) __hip_atomic_fetch_add(&a.head->findings, n_find, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(256) digest_verify_kernel(DigestArgs a, PackGeom p) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, grp = a.c0 / 64u + blockIdx.y;
+  const uint64_t unit = digest_unit_rows(p), stride = (uint64_t)kDigestWaves * gridDim.x * unit;
+  for (uint64_t row0 = ((uint64_t)blockIdx.x * kDigestWaves + wave) * unit; row0 < a.cols.rows; row0 += stride) {  // wave-uniform
+    uint32_t x[kDigestRounds];
+#pragma unroll
+    for (uint32_t t = 0; t < kDigestRounds; ++t) {
+      const DigestLane L = digest_lane(p, a.cols.rows, a.c0, a.c1, grp, row0, t, lane);
+      x[t] = L.on ? __builtin_nontemporal_load(a.words + L.row * a.npol + L.col) : 0u;
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < kDigestRounds; ++t) {
+      const uint32_t v = x[t];
+      if (!digest_finding(v) || digest_wide(v) || (digest_need(digest_kind(KW_REASON(v))) & ~a.loaded)) continue;
+      const DigestLane L = digest_lane(p, a.cols.rows, a.c0, a.c1, grp, row0, t, lane);
+      const DigestKey key = digest_key(a.cols, L.row, v);
+      const uint64_t i = digest_slot(a, digest_tag(digest_hash(L.col, digest_class(v), key), a.hash_bits), false);
+      bool same = false;
+      if (i != kDigestNone) {
+        const uint64_t rep = digest_load(&a.table[i].rep), rrow = digest_rep_row(rep);
+        const uint32_t rcol = digest_rep_col(rep);
+        if (rrow == (a.d2b ? a.d2b[L.row] : L.row) && rcol == L.col) continue;  // the representative itself
+        if (rrow < a.cols.rows && rcol == L.col) {
+          const uint64_t drow = a.b2d ? a.b2d[rrow] : rrow;
+          const uint32_t rw = a.words[drow * a.npol + rcol];
+          same = digest_finding(rw) && !digest_wide(rw) && digest_class(rw) == digest_class(v) &&
+                 digest_same_key(key, digest_key(a.cols, drow, rw));
+        }
+      }
+      if (same) continue;
+      const uint64_t n = __hip_atomic_fetch_add(&a.head->nleft, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (n < a.left_cap) {
+        DigestLeft e;
+        e.pair = L.row * a.npol + L.col;
+        e.word = v;
+        e.pad = 0;
+        a.left[n] = e;
+      }
+      if (i != kDigestNone) __hip_atomic_fetch_add(&a.table[i].count, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) digest_gather_kernel(DigestArgs a) {
+  const uint64_t nt = (uint64_t)gridDim.x * 256u;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.nslots; i += nt) {
+    const DigestSlot sl = a.table[i];
+    if (sl.tag == 0u || sl.count == 0u) continue;
+    const uint64_t row = digest_rep_row(sl.rep);
+    const uint32_t col = digest_rep_col(sl.rep);
+    if (row >= a.cols.rows || col >= a.npol) continue;  // (only a range the host discards holds such a slot)
+    const uint64_t n = __hip_atomic_fetch_add(&a.head->nrec, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (n >= a.rec_cap) continue;
+    kw_digest_rec r;
+    r.col = col;
+    r.word = a.words[(a.b2d ? a.b2d[row] : row) * a.npol + col];
+    r.first_row = row;
+    r.count = sl.count;
+    a.recs[n] = r;
+  }
+}
+
+namespace {
+bool digest_grid(const DigestArgs& a, dim3* grid) {
+  if (a.cols.rows == 0 || a.npol == 0 || a.c0 >= a.c1 || a.c1 > a.npol) return false;
+  const uint64_t unit = digest_unit_rows(pack_geom(a.npol)), nunits = (a.cols.rows + unit - 1u) / unit;
+  const uint64_t want = (nunits + kDigestWaves - 1u) / kDigestWaves, most = (uint64_t)std::max<uint32_t>(device_cus(), 1u) * 8u;
+  *grid = dim3((uint32_t)std::min(want, most), (a.c1 - 1u) / 64u - a.c0 / 64u + 1u);
+  return true;
+}
+}  // namespace
+
+hipError_t launch_digest_count(const DigestArgs& a, hipStream_t s) {
+  dim3 grid;
+  if (!digest_grid(a, &grid)) return hipSuccess;
+  if (grid.y > 65535u || (a.nslots & (a.nslots - 1u)) || a.nslots == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(digest_count_kernel, grid, dim3(256), 0, s, a, pack_geom(a.npol));
+  return hipGetLastError();
+}
+
+hipError_t launch_digest_verify(const DigestArgs& a, hipStream_t s) {
+  dim3 grid;
+  if (!digest_grid(a, &grid)) return hipSuccess;
+  if (grid.y > 65535u || (a.nslots & (a.nslots - 1u)) || a.nslots == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(digest_verify_kernel, grid, dim3(256), 0, s, a, pack_geom(a.npol));
+  return hipGetLastError();
+}
+
+hipError_t launch_digest_gather(const DigestArgs& a, hipStream_t s) {
+  if (a.nslots == 0 || a.cols.rows == 0) return hipSuccess;
+  const uint64_t most = (uint64_t)std::max<uint32_t>(device_cus(), 1u) * 8u;
+  hipLaunchKernelGGL(digest_gather_kernel, dim3((uint32_t)std::min<uint64_t>(most, (a.nslots + 255u) / 256u)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_overflow(const EvalArgs& a, const TileArgs* d_t, const uint32_t* d_overflow, uint32_t n_overflow,
                            hipStream_t s) {
   if (n_overflow == 0 || a.nrows == 0) return hipSuccess;

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "digest.hpp"
 #include "kwdev.hpp"
 #include "outcomes.hpp"
 #include "packed.hpp"
@@ -499,6 +500,41 @@ struct OutcomeArgs {
   uint32_t g0;            // the range's first group: unit group g counts into table row g - g0
 };
 hipError_t launch_outcomes(const OutcomeArgs& a, hipStream_t s);
+
+// The violation digest (kw_batch_digest; the key, the hash and the table: digest.hpp): three launches
+// over one column range [c0, c1) of the verdict words, none waiting on another workgroup.
+//   count    the words walked with the summary's geometry (a lane keeps a column, grid.y the column
+//            groups of 64, a wave strides over units of kDigestRounds rounds). Findings are sparse: a
+//            lane that holds one reads its key bytes from the HBM columns through the offset arrays
+//            (plain vector loads), hashes (column, class, key) and holds the findings of its column's
+//            four busiest tags in registers; an evicted run goes to its slot: the tag claimed by a 64-bit compare-and-swap, the
+//            count by a 64-bit add, the representative by a 64-bit unsigned max that a plain load
+//            skips when it cannot win. Wide findings append their pair index through one counter.
+//   verify   a launch of its own, so every representative is final: each finding finds its slot
+//            again and compares its column, class and key bytes with the representative's; on a
+//            mismatch it goes to the bounded leftover list and its slot's count drops by one.
+//   gather   the live slots into records, in any order (the host sorts).
+// Relaxed agent-scope vector atomics and plain vector stores only; the stream orders the launches, the
+// zeroing before and the read-back after. Integer adds and a max: the table's final state does not
+// depend on the order in which the waves arrive.
+struct DigestArgs {
+  const uint32_t* words;  // [rows][npol], device-row order
+  DigestCols cols;        // the device columns (device rows)
+  const uint32_t* d2b;    // the batch row of each device row, nullptr: the same
+  const uint32_t* b2d;    // and the reverse
+  DigestSlot* table;
+  DigestHead* head;
+  uint64_t* wide;         // [wide_cap] device pair indices
+  DigestLeft* left;       // [left_cap]
+  kw_digest_rec* recs;    // [rec_cap] (gather)
+  uint64_t nslots, wide_cap, rec_cap;
+  uint32_t left_cap, hash_bits;
+  uint32_t npol, c0, c1;
+  uint32_t loaded;        // string columns (bits of Str) that are resident
+};
+hipError_t launch_digest_count(const DigestArgs& a, hipStream_t s);
+hipError_t launch_digest_verify(const DigestArgs& a, hipStream_t s);
+hipError_t launch_digest_gather(const DigestArgs& a, hipStream_t s);
 
 hipError_t launch_nfa_classify(const EvalArgs& a, const TileArgs* d_t, const NfaPass& np, uint32_t threads, hipStream_t s);
 // threads of the NFA pass's grid for `items` entities within a scratch budget

@@ -21,6 +21,7 @@ enum Knob : int {
   KW_SCHED, KW_SCHED_TAIL, KW_SPLIT, KW_GROUP_FORM, KW_POISON_VERDICTS, KW_FLATTEN_THREADS,
   KW_SLOT_ROWS, KW_HEAVY_ROWS, KW_HEAVY_CTR, KW_GLOBAL_TABLES, KW_TILE_SPLIT, KW_ROUND_SPLIT,
   KW_TILE_QUANTILE, KW_TILE_DEBUG, KW_TILE_CUT, KW_OUTCOME_TABLE, KW_TILE_GENERIC,
+  KW_DIGEST_TABLE, KW_DIGEST_HASH_BITS,
   KW_NKNOBS
 };
 
@@ -87,6 +88,8 @@ constexpr KnobRow kKnobs[KW_NKNOBS] = {
     knob_flag("KW_TILE_CUT", KnobKind::On, kLive, kPlans, "end each tile at the row of least estimated cost per row (0: fixed height)"),
     knob_int("KW_OUTCOME_TABLE", kLive, kNoPlan, 64 << 20, 1, INT_MAX, kClamp, "kw_batch_outcomes: bytes of the device table (more groups are counted in ranges)"),
     knob_flag("KW_TILE_GENERIC", KnobKind::Off, kLive, kPlans, "every tile launch on the generic kernel, none on a production-shape one"),
+    knob_int("KW_DIGEST_TABLE", kLive, kNoPlan, 64 << 20, 1, INT_MAX, kClamp, "kw_batch_digest: bytes of the device hash table (more groups are reduced in column ranges)"),
+    knob_int("KW_DIGEST_HASH_BITS", kLive, kNoPlan, 64, 0, 64, kClamp, "kw_batch_digest: low bits of the key hash that are kept (tests: fewer make every probe collide)"),
 };
 
 constexpr bool knob_name_is(const char* a, const char* b) {
@@ -101,6 +104,7 @@ KW_KNOB_ROW(KW_SCHED); KW_KNOB_ROW(KW_SCHED_TAIL); KW_KNOB_ROW(KW_SPLIT); KW_KNO
 KW_KNOB_ROW(KW_FLATTEN_THREADS); KW_KNOB_ROW(KW_SLOT_ROWS); KW_KNOB_ROW(KW_HEAVY_ROWS); KW_KNOB_ROW(KW_HEAVY_CTR);
 KW_KNOB_ROW(KW_GLOBAL_TABLES); KW_KNOB_ROW(KW_TILE_SPLIT); KW_KNOB_ROW(KW_ROUND_SPLIT); KW_KNOB_ROW(KW_TILE_QUANTILE);
 KW_KNOB_ROW(KW_TILE_DEBUG); KW_KNOB_ROW(KW_TILE_CUT); KW_KNOB_ROW(KW_OUTCOME_TABLE); KW_KNOB_ROW(KW_TILE_GENERIC);
+KW_KNOB_ROW(KW_DIGEST_TABLE); KW_KNOB_ROW(KW_DIGEST_HASH_BITS);
 #undef KW_KNOB_ROW
 
 // The plan cache's key for the KW_* settings (tests switch them between passes): the current

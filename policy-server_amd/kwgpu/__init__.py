@@ -10,6 +10,7 @@ reference so tests read like its own:
 
 Every evaluation runs on the GPU through the C ABI; nothing here computes a verdict.
 """
+import collections
 import ctypes as C
 import json
 
@@ -438,6 +439,19 @@ class NoSpace(Exception):
         self.need = int(need)
 
 
+class DigestNoSpace(NoSpace):
+    """KW_E_NOSPACE of a violation digest: .need records and .need_wide wide pairs are required."""
+
+    def __init__(self, need, need_wide):
+        Exception.__init__(self, f"the digest needs {need} records and {need_wide} wide pairs")
+        self.need, self.need_wide = int(need), int(need_wide)
+
+
+# kw_digest_rec as a numpy structured dtype (24 bytes, no padding)
+DIGEST_REC = [("col", "<u4"), ("word", "<u4"), ("first_row", "<u8"), ("count", "<u8")]
+Digest = collections.namedtuple("Digest", ["recs", "wide", "findings"])
+
+
 class Batch:
     """A micro-batch of requests in SoA form (kw_batch)."""
 
@@ -678,6 +692,70 @@ class Batch:
         raise_for(N.lib().kw_debug_outcome_words(words.ctypes.data_as(C.POINTER(C.c_uint32)), rows, npol, ptr, ngroups,
                                                  out.ctypes.data_as(C.POINTER(C.c_uint64))), "kw_debug_outcome_words failed")
         return out
+
+    @staticmethod
+    def _digest_call(call, cap, wide_cap, grow):
+        """call(struct) with arrays of cap / wide_cap entries; on KW_E_NOSPACE once more with the
+        reported need when `grow`, else DigestNoSpace."""
+        import numpy as np
+        for attempt in (0, 1):
+            recs = np.zeros(max(cap, 1), dtype=np.dtype(DIGEST_REC))
+            wide = np.zeros(max(wide_cap, 1), dtype=np.uint64)
+            st = N.KwDigest(recs.ctypes.data_as(C.POINTER(N.KwDigestRec)), cap, 0,
+                            wide.ctypes.data_as(C.POINTER(C.c_uint64)), wide_cap, 0, 0)
+            rc = call(C.byref(st))
+            if rc != N.KW_E_NOSPACE:
+                break
+            if not grow or attempt or (st.n <= cap and st.nwide <= wide_cap):
+                raise DigestNoSpace(st.n, st.nwide)
+            cap, wide_cap = max(cap, st.n), max(wide_cap, st.nwide)
+        raise_for(rc, "the violation digest failed")
+        return Digest(recs[:st.n], wide[:st.nwide], int(st.findings))
+
+    def digest(self, cap=None, wide_cap=None):
+        """The violation digest of the last all-pairs device pass (kw_batch_digest), reduced on the
+        device: Digest(recs, wide, findings) with recs a structured array (col, word, first_row, count)
+        of the groups ordered by (col, reason, first_row) and wide the pair indices row * npol + col of
+        the findings whose argument is in the pass's side data. Without `cap` the arrays start at 4096
+        records / 1024 pairs and grow once to the reported need; with it a pass that needs more raises
+        DigestNoSpace (.need, .need_wide)."""
+        grow = cap is None and wide_cap is None
+        return self._digest_call(lambda st: self._L.kw_batch_digest(self._h, st), 4096 if cap is None else cap,
+                                 1024 if wide_cap is None else wide_cap, grow)
+
+    def digest_from_words(self, words, npol, cap=None, wide_cap=None):
+        """Diagnostic (kw_debug_digest_words): the same digest from full words [rows][npol] over this
+        batch's host columns, by the reference reducer (an ordered map over the exact keys)."""
+        import numpy as np
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        rows = words.size // npol
+        ptr = words.ctypes.data_as(C.POINTER(C.c_uint32))
+        grow = cap is None and wide_cap is None
+        return self._digest_call(lambda st: self._L.kw_debug_digest_words(self._h, ptr, rows, npol, st),
+                                 4096 if cap is None else cap, 1024 if wide_cap is None else wide_cap, grow)
+
+    def finding_key(self, row, word):
+        """The key bytes of the finding `word` at batch row `row` (kw_batch_finding_key), host only:
+        (key, value) for KW_R_LABEL_CONSTRAINT, else (key, None); a numeric or empty key is b""."""
+        need, split = C.c_size_t(), C.c_size_t()
+        buf = C.create_string_buffer(256)
+        rc = self._L.kw_batch_finding_key(self._h, row, int(word), buf, len(buf), C.byref(need), C.byref(split))
+        if rc == N.KW_E_NOSPACE:
+            buf = C.create_string_buffer(need.value + 1)
+            rc = self._L.kw_batch_finding_key(self._h, row, int(word), buf, len(buf), C.byref(need), C.byref(split))
+        raise_for(rc, "kw_batch_finding_key failed")
+        raw = buf.raw[:need.value]
+        if ((int(word) >> 8) & 0xff) == 11:
+            return raw[:split.value], raw[split.value:]
+        return raw, None
+
+    def debug_digest_stats(self):
+        """Diagnostic (kw_debug_digest_stats): what the last digest() did, as a dict: the column
+        ranges that ran, the findings the verify launch handed to the host, the table's slots, the
+        ranges that were cut."""
+        out = (C.c_uint64 * 4)()
+        raise_for(self._L.kw_debug_digest_stats(self._h, out), "the batch was never digested")
+        return dict(zip(("ranges", "leftovers", "slots", "cuts"), out))
 
     def debug_plan(self, env, policies, origin=VALIDATE):
         """Diagnostic (kw_debug_plan): the tile kernel's plan for an all-pairs pass, on the host."""

@@ -105,6 +105,18 @@ class KwSummary(C.Structure):
                 ("planes", C.POINTER(C.c_uint64))]
 
 
+class KwDigestRec(C.Structure):
+    """kw_digest_rec: one group of the violation digest (include/kwgpu.h)."""
+    _fields_ = [("col", C.c_uint32), ("word", C.c_uint32), ("first_row", C.c_uint64), ("count", C.c_uint64)]
+
+
+class KwDigest(C.Structure):
+    """kw_digest: the violation digest of a pass (include/kwgpu.h)."""
+    _fields_ = [("recs", C.POINTER(KwDigestRec)), ("cap", C.c_size_t), ("n", C.c_size_t),
+                ("wide", C.POINTER(C.c_uint64)), ("wide_cap", C.c_size_t), ("nwide", C.c_size_t),
+                ("findings", C.c_uint64)]
+
+
 EXPORTS = [
     "kw_env_build", "kw_env_build_yaml", "kw_yaml_to_json", "kw_env_serialize", "kw_env_deserialize", "kw_env_destroy", "kw_env_lookup",
     "kw_env_policy_count", "kw_env_policy_id", "kw_env_is_group", "kw_env_get_policy_mode",
@@ -119,6 +131,7 @@ EXPORTS = [
     "kw_packed_unpack", "kw_debug_pack_words", "kw_batch_summary", "kw_validate_host_summary", "kw_batch_verdict_rows",
     "kw_batch_last_pass",
     "kw_debug_summarize_words", "kw_batch_outcomes", "kw_debug_outcome_words", "kw_batch_attribute_groups",
+    "kw_batch_digest", "kw_debug_digest_words", "kw_batch_finding_key", "kw_debug_digest_stats",
     "kw_metrics_add_outcomes", "kw_metrics_record_pass", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
     "kw_batch_destroy", "kw_debug_host_walk", "kw_validate_batch", "kw_validate_rows", "kw_batch_verdicts",
     "kw_validate_timed", "kw_format_response", "kw_format_response_doc", "kw_env_group_members", "kw_evaluate",
@@ -207,6 +220,10 @@ def lib():
         "kw_batch_outcomes": (ip, [vp, C.POINTER(u32), u32, C.POINTER(u64)]),
         "kw_debug_outcome_words": (ip, [C.POINTER(u32), u64, u32, C.POINTER(u32), u32, C.POINTER(u64)]),
         "kw_batch_attribute_groups": (ip, [vp, C.POINTER(u32), C.POINTER(u64), sz, C.POINTER(u32)]),
+        "kw_batch_digest": (ip, [vp, C.POINTER(KwDigest)]),
+        "kw_debug_digest_words": (ip, [vp, C.POINTER(u32), u64, u32, C.POINTER(KwDigest)]),
+        "kw_batch_finding_key": (ip, [vp, u64, u32, cp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "kw_debug_digest_stats": (ip, [vp, C.POINTER(u64)]),
         "kw_metrics_add_outcomes": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64, C.POINTER(u64), u32, C.POINTER(u64)]),
         "kw_metrics_record_pass": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64]),
         "kw_batch_pin_host": (ip, [vp, ip]),
