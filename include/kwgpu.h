@@ -343,6 +343,30 @@ int kw_debug_prod_shape(uint32_t feat, int lds_tables, uint32_t debug, uint32_t 
 int kw_debug_plan_kernels(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
                           uint32_t *out, size_t cap, size_t *needed);
 
+/* Diagnostic (tests): beside kw_debug_last_launches, the variant each of those launches asked the tile
+ * kernel's dispatch for, recorded where the launch is made, one word each: bits 0-5 the launch's
+ * family and flag bits (the family bits of kw_debug_tile_cost, 16 NFA elements, 32 predecessor ranges
+ * by wave scan), KW_VARIANT_LDS_TABLES, KW_VARIANT_TIMING (the phase clocks run), KW_VARIANT_PROD (the
+ * production shape). *needed: words; KW_E_NOSPACE when cap is smaller; KW_E_ARG for a batch that is
+ * not resident. */
+#define KW_VARIANT_FEAT 0x3fu
+#define KW_VARIANT_LDS_TABLES 0x100u
+#define KW_VARIANT_TIMING 0x200u
+#define KW_VARIANT_PROD 0x400u
+int kw_debug_last_variants(const kw_batch *b, uint32_t *out, size_t cap, size_t *needed);
+
+/* Diagnostic (tests): the variant (as kw_debug_last_variants) each tile launch of a resident all-pairs
+ * pass would ask for under the current settings, planned over the batch's host columns (nothing
+ * launched, no device needed), in launch order. *needed: words; KW_E_NOSPACE when cap is smaller. */
+int kw_debug_plan_variants(const kw_env *env, kw_batch *b, const int32_t *policies, uint32_t npol, int origin,
+                           uint32_t *out, size_t cap, size_t *needed);
+
+/* Diagnostic (tests): the instantiation of the tile kernel the dispatch resolves a requested variant
+ * to, as a variant word: several requests share one instantiation (the phase clocks keep three family
+ * sets with LDS tables and run every other set on the every-family kernel; an NFA element takes the
+ * every-family kernel). The dispatch itself picks the kernel by this function. */
+uint32_t kw_debug_resolve_variant(uint32_t variant);
+
 /* Diagnostic (tests): the device-row order kw_batch_to_device gives this batch — the light / heavy
  * split (rows with more than 5 containers after the others when they are 1-50 % of
  * a batch of >= 2^18 rows and hold >= 30 % of its containers; KW_SPLIT=0 / 1 never / always) — as a

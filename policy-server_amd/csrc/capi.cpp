@@ -756,6 +756,36 @@ int kw_debug_plan_kernels(const kw_env* env, kw_batch* kb, const int32_t* polici
   return KW_OK;
 }
 
+int kw_debug_last_variants(const kw_batch* kb, uint32_t* out, size_t cap, size_t* needed) {
+  if (!kb || !kb->dev || !needed || (!out && cap)) return KW_E_ARG;
+  const std::vector<uint32_t>& v = kb->dev->last_variants;
+  *needed = v.size();
+  if (cap < v.size()) return KW_E_NOSPACE;
+  std::copy(v.begin(), v.end(), out);
+  return KW_OK;
+}
+
+int kw_debug_plan_variants(const kw_env* env, kw_batch* kb, const int32_t* policies, uint32_t npol, int origin, uint32_t* out,
+                           size_t cap, size_t* needed) {
+  if (!env || !kb || !needed || (!out && cap) || (!policies && npol)) return KW_E_ARG;
+  std::unique_ptr<DeviceBatch> saved = std::move(kb->dev);
+  kb->dev = host_view(kb);
+  PassPlan plan;
+  const int rc = plan_pass(env, kb, policies, npol, nullptr, origin, false, &plan);
+  std::vector<uint32_t> w;
+  if (rc == KW_OK)
+    for (const TileArgs& t : plan.tiles) w.push_back(tile_variant_word(tile_variant(t, (t.debug & 512u) != 0)));
+  kb->dev->verdicts = nullptr;  // host memory: not the DeviceBatch's to free
+  kb->dev = std::move(saved);
+  if (rc) return rc;
+  *needed = w.size();
+  if (cap < w.size()) return KW_E_NOSPACE;
+  std::copy(w.begin(), w.end(), out);
+  return KW_OK;
+}
+
+uint32_t kw_debug_resolve_variant(uint32_t variant) { return tile_variant_word(tile_resolve(tile_variant_of(variant))); }
+
 int kw_debug_reorder(const kw_batch* kb, uint64_t* perm, size_t cap, uint64_t* split, kw_batch** out) {
   if (!kb || !split || !out || (!perm && kb->b.n) || cap < kb->b.n) return KW_E_ARG;
   std::vector<uint64_t> p;

@@ -150,6 +150,7 @@ struct DeviceBatch {
   uint32_t* sched = nullptr;  // tile counters (zeroed once; each launch leaves them zero)
   std::vector<int64_t> last_launches;  // the last pass's tile launches: (workgroups launched, descriptors, static rounds or -1) each (diagnostic)
   std::vector<uint32_t> last_kernels;  // the kernel each of those launches took (kernels.hpp tile_kernel_kind)
+  std::vector<uint32_t> last_variants;  // and the variant each asked the dispatch for (kernels.hpp tile_variant_word)
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   // the last pass's plan as the kernels read it (host copies detect a changed plan)
   TileArgs* d_tiles = nullptr;

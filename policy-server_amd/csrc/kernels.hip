@@ -1829,26 +1829,27 @@ constexpr std::array<const void*, sizeof...(Fs)> tile_fns() {
 }
 // prod: the launch has the production shape (tile_prod_shape, which admits only the two family sets
 // below, LDS tables and no timing), and takes the instantiation with that shape compiled in.
+// Which instantiation a request takes is tile_resolve's (kernels.hpp) to say, and the tests read it
+// there (kw_debug_resolve_variant); this function only maps a resolved variant to its kernel.
 const void* tile_fn(bool ldst, bool timing, uint32_t feat, bool prod) {
-  if (prod)
-    return (feat & kFeatRng) ? (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr | kFeatRng, true>
-                             : (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr, true>;
+  const TileVariant v = tile_resolve(TileVariant{ldst, timing, feat, prod});
+  if (v.prod)
+    return (v.feat & kFeatRng) ? (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr | kFeatRng, true>
+                               : (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr, true>;
   static const auto g = tile_fns<false, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>();
   static const auto l = tile_fns<true, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>();
-  if (feat & kFeatNfa)  // the one instantiation with NFA elements: every family (timing runs it too)
-    return ldst ? (const void*)evaluate_tiles_kernel<true, false, kFeatAll | kFeatNfa>
-                : (const void*)evaluate_tiles_kernel<false, false, kFeatAll | kFeatNfa>;
-  if ((feat & kFeatRng) && ldst && !timing && (feat & kFeatAll) == (kFeatLbl | kFeatCtr))
-    return (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr | kFeatRng>;
-  if (timing) {  // diagnostics: the C2 / C3 / C4 family sets with LDS tables (same registers as the product), else every family
-    if (ldst && (feat & kFeatAll) == kFeatImg) return (const void*)evaluate_tiles_kernel<true, true, kFeatImg>;
-    if (ldst && (feat & kFeatAll) == (kFeatImg | kFeatGrp)) return (const void*)evaluate_tiles_kernel<true, true, kFeatImg | kFeatGrp>;
-    if (ldst && (feat & kFeatAll) == (kFeatLbl | kFeatCtr)) return (const void*)evaluate_tiles_kernel<true, true, kFeatLbl | kFeatCtr>;
-    return ldst ? (const void*)evaluate_tiles_kernel<true, true, kFeatAll> : (const void*)evaluate_tiles_kernel<false, true, kFeatAll>;
+  if (v.feat & kFeatNfa)  // the one instantiation with NFA elements: every family (timing runs it too)
+    return v.ldst ? (const void*)evaluate_tiles_kernel<true, false, kFeatAll | kFeatNfa>
+                  : (const void*)evaluate_tiles_kernel<false, false, kFeatAll | kFeatNfa>;
+  if (v.feat & kFeatRng) return (const void*)evaluate_tiles_kernel<true, false, kFeatLbl | kFeatCtr | kFeatRng>;
+  if (v.timing) {  // diagnostics: the C2 / C3 / C4 family sets with LDS tables (same registers as the product), else every family
+    if (v.feat == kFeatImg) return (const void*)evaluate_tiles_kernel<true, true, kFeatImg>;
+    if (v.feat == (kFeatImg | kFeatGrp)) return (const void*)evaluate_tiles_kernel<true, true, kFeatImg | kFeatGrp>;
+    if (v.feat == (kFeatLbl | kFeatCtr)) return (const void*)evaluate_tiles_kernel<true, true, kFeatLbl | kFeatCtr>;
+    return v.ldst ? (const void*)evaluate_tiles_kernel<true, true, kFeatAll> : (const void*)evaluate_tiles_kernel<false, true, kFeatAll>;
   }
-  return ldst ? l[feat & kFeatAll] : g[feat & kFeatAll];
+  return v.ldst ? l[v.feat] : g[v.feat];
 }
-uint32_t tile_feat(const TileArgs& t) { return t.feat & (kFeatAll | kFeatNfa | kFeatRng); }
 
 hipError_t ensure_attrs() {
   int dev = 0;
@@ -1912,8 +1913,8 @@ hipError_t launch_evaluate_tiles(const EvalArgs& a, const TileArgs& t, const Til
   if (hipError_t e = ensure_attrs(); e != hipSuccess) return e;
   grid = tile_launch_grid(t, a.phase != nullptr, grid, /*print=*/true);  // (an already clamped grid stays as it is)
   using TileFn = void (*)(EvalArgs, const TileArgs*, const TileDesc*);
-  const TileFn fn = (TileFn)tile_fn(t.lds_tables != 0, a.phase != nullptr, tile_feat(t),
-                                    tile_kernel_kind(t, a.phase != nullptr) == kTileKernelProd);
+  const TileVariant v = tile_variant(t, a.phase != nullptr);  // (what the pass records per launch: pass.cpp run_pass)
+  const TileFn fn = (TileFn)tile_fn(v.ldst, v.timing, v.feat, v.prod);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(kSlotThreads), t.lds_bytes, s, a, d_t, d_desc);
   return hipGetLastError();
 }

@@ -332,6 +332,44 @@ uint32_t tile_launch_grid(const TileArgs& t, bool timing, uint32_t grid, bool pr
 constexpr uint32_t kTileKernelGeneric = 0, kTileKernelProd = 1;
 uint32_t tile_kernel_kind(const TileArgs& t, bool timing);
 
+// The variant of a launch: the four arguments the dispatch (kernels.hip tile_fn) is called with, as
+// one word (kw_debug_last_variants, kw_debug_plan_variants): bits 0-5 the family and flag bits
+// feat & (kFeatAll | kFeatNfa | kFeatRng), then LDS tables, phase clocks, production shape.
+struct TileVariant {
+  bool ldst, timing;
+  uint32_t feat;
+  bool prod;
+};
+constexpr uint32_t kVarFeatMask = kFeatAll | kFeatNfa | kFeatRng, kVarLdst = 1u << 8, kVarTiming = 1u << 9, kVarProd = 1u << 10;
+constexpr uint32_t tile_variant_word(const TileVariant& v) {
+  return (v.feat & kVarFeatMask) | (v.ldst ? kVarLdst : 0u) | (v.timing ? kVarTiming : 0u) | (v.prod ? kVarProd : 0u);
+}
+constexpr TileVariant tile_variant_of(uint32_t w) {
+  return TileVariant{(w & kVarLdst) != 0, (w & kVarTiming) != 0, w & kVarFeatMask, (w & kVarProd) != 0};
+}
+inline uint32_t tile_feat(const TileArgs& t) { return t.feat & kVarFeatMask; }
+// What a launch of `t` asks the dispatch for.
+inline TileVariant tile_variant(const TileArgs& t, bool timing) {
+  return TileVariant{t.lds_tables != 0, timing, tile_feat(t), tile_kernel_kind(t, timing) == kTileKernelProd};
+}
+// The instantiation evaluate_tiles_kernel<ldst, timing, feat, prod> a request resolves to: several
+// requests share one (the production shape has LDS tables and no clocks; an NFA element takes the
+// every-family kernel, clocks or not; the wave scan exists for the label / container set with LDS
+// tables and no clocks; the clocks keep the C2 / C3 / C4 family sets with LDS tables and run every
+// other set on the every-family kernel). tile_fn picks the kernel by this function's result alone.
+constexpr TileVariant tile_resolve(const TileVariant& v) {
+  const uint32_t fam = v.feat & kFeatAll;
+  if (v.prod) return TileVariant{true, false, kFeatLbl | kFeatCtr | (v.feat & kFeatRng), true};
+  if (v.feat & kFeatNfa) return TileVariant{v.ldst, false, kFeatAll | kFeatNfa, false};
+  if ((v.feat & kFeatRng) && v.ldst && !v.timing && fam == (kFeatLbl | kFeatCtr))
+    return TileVariant{true, false, kFeatLbl | kFeatCtr | kFeatRng, false};
+  if (v.timing) {
+    const bool own = v.ldst && (fam == kFeatImg || fam == (kFeatImg | kFeatGrp) || fam == (kFeatLbl | kFeatCtr));
+    return TileVariant{v.ldst, true, own ? fam : kFeatAll, false};
+  }
+  return TileVariant{v.ldst, false, fam, false};
+}
+
 // One launch of the tile kernel over chunks t.chunk[0..nchunk). t: host copy (launch geometry);
 // d_t: the same TileArgs resident in device memory (read by the kernel).
 hipError_t launch_evaluate_tiles(const EvalArgs& a, const TileArgs& t, const TileArgs* d_t, const TileDesc* d_desc,

@@ -479,6 +479,7 @@ static int run_pass(kw_batch* kb, PassPlan& plan, bool timed, hipStream_t s) {
   const size_t nl = plan.launches.size();
   D.last_launches.clear();
   D.last_kernels.clear();
+  D.last_variants.clear();
   for (size_t l = 0; l < plan.tiles.size(); ++l) {
     const size_t k = l / nl;
     if (phases) HIPCHK(hipMemsetAsync(d_phase, 0, phase_bytes, s));
@@ -494,6 +495,7 @@ static int run_pass(kw_batch* kb, PassPlan& plan, bool timed, hipStream_t s) {
     else Ak.sched_static = (uint32_t)S;
     for (int64_t v : {(int64_t)grid, (int64_t)Ak.ndesc, (int64_t)S}) D.last_launches.push_back(v);
     D.last_kernels.push_back(tile_kernel_kind(plan.tiles[l], phases));
+    D.last_variants.push_back(tile_variant_word(tile_variant(plan.tiles[l], phases)));
     HIPCHK(launch_evaluate_tiles(Ak, plan.tiles[l], D.d_tiles + l, D.desc + D.reg_desc[k], grid, s));
     if (phases) {
       std::vector<uint64_t> ph((size_t)grid * kPhaseWords);

@@ -21,6 +21,29 @@ PROTECT, MONITOR = N.KW_MODE_PROTECT, N.KW_MODE_MONITOR
 VALIDATE, AUDIT = N.KW_ORIGIN_VALIDATE, N.KW_ORIGIN_AUDIT
 # the tile kernel a launch took (Batch.debug_last_kernels): the generic one, or the production-shape one
 KERNEL_GENERIC, KERNEL_PROD = 0, 1
+# family and flag bits of a tile launch (Variant.feat): image, label, container, group families; NFA
+# elements; predecessor ranges by wave scan
+FEAT_IMG, FEAT_LBL, FEAT_CTR, FEAT_GRP, FEAT_NFA, FEAT_RNG = 1, 2, 4, 8, 16, 32
+FEAT_ALL = 15
+
+
+class Variant(collections.namedtuple("Variant", "feat lds_tables timing prod")):
+    """What a tile launch asks the kernel's dispatch for (Batch.debug_last_variants,
+    debug_plan_variants): the family and flag bits, LDS or global tables, phase clocks, production
+    shape. resolve(): the instantiation of the kernel that request takes (kw_debug_resolve_variant)."""
+    __slots__ = ()
+
+    @classmethod
+    def from_word(cls, w):
+        return cls(w & N.KW_VARIANT_FEAT, bool(w & N.KW_VARIANT_LDS_TABLES), bool(w & N.KW_VARIANT_TIMING),
+                   bool(w & N.KW_VARIANT_PROD))
+
+    def word(self):
+        return (self.feat | (N.KW_VARIANT_LDS_TABLES if self.lds_tables else 0) | (N.KW_VARIANT_TIMING if self.timing else 0) |
+                (N.KW_VARIANT_PROD if self.prod else 0))
+
+    def resolve(self):
+        return Variant.from_word(N.lib().kw_debug_resolve_variant(self.word()))
 
 
 class RequestOrigin:
@@ -834,6 +857,32 @@ class Batch:
         raise_for(self._L.kw_debug_plan_kernels(env._h, self._h, arr, len(policies), origin, out, need.value, C.byref(need)),
                   "kw_debug_plan_kernels failed")
         return list(out)
+
+    def debug_last_variants(self):
+        """Diagnostic (kw_debug_last_variants): beside debug_last_launches, the Variant each launch
+        of the batch's last resident pass asked the tile kernel's dispatch for."""
+        need = C.c_size_t()
+        rc = self._L.kw_debug_last_variants(self._h, None, 0, C.byref(need))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_debug_last_variants failed")
+            return []
+        out = (C.c_uint32 * need.value)()
+        raise_for(self._L.kw_debug_last_variants(self._h, out, need.value, C.byref(need)), "kw_debug_last_variants failed")
+        return [Variant.from_word(w) for w in out]
+
+    def debug_plan_variants(self, env, policies, origin=VALIDATE):
+        """Diagnostic (kw_debug_plan_variants): the Variant each tile launch of a resident
+        all-pairs pass would ask for under the current settings, planned on the host."""
+        arr = env._array(policies)
+        need = C.c_size_t()
+        rc = self._L.kw_debug_plan_variants(env._h, self._h, arr, len(policies), origin, None, 0, C.byref(need))
+        if rc != N.KW_E_NOSPACE:
+            raise_for(rc, "kw_debug_plan_variants failed")
+            return []
+        out = (C.c_uint32 * need.value)()
+        raise_for(self._L.kw_debug_plan_variants(env._h, self._h, arr, len(policies), origin, out, need.value, C.byref(need)),
+                  "kw_debug_plan_variants failed")
+        return [Variant.from_word(w) for w in out]
 
     def debug_reorder(self):
         """Diagnostic (kw_debug_reorder): the device-row order kw_batch_to_device gives this batch,

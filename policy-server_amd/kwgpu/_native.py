@@ -55,6 +55,9 @@ KW_SUM_N = 32
 KW_OUT_REJECTED, KW_OUT_ACCEPTED, KW_OUT_MUTATED, KW_OUT_ERROR_500, KW_OUT_INIT_ERROR = 0, 1, 2, 4, 8
 KW_OUT_N = 9
 
+# a tile launch's variant word (kwgpu.h kw_debug_last_variants)
+KW_VARIANT_FEAT, KW_VARIANT_LDS_TABLES, KW_VARIANT_TIMING, KW_VARIANT_PROD = 0x3F, 0x100, 0x200, 0x400
+
 REASONS = {
     0: "NONE", 1: "PRIVILEGED", 2: "NAMESPACE", 3: "REG_NOT_ALLOWED", 4: "REG_REJECTED",
     5: "TAG_REJECTED", 6: "IMG_NOT_ALLOWED", 7: "IMG_REJECTED", 8: "CAP_NOT_ALLOWED",
@@ -125,7 +128,8 @@ EXPORTS = [
     "kw_env_policy_initialization_error", "kw_env_validate_settings", "kw_pattern_match", "kw_pattern_match_many", "kw_env_pattern_count",
     "kw_env_pattern", "kw_env_classify", "kw_batch_wide_arg", "kw_batch_group_causes", "kw_debug_plan", "kw_debug_copy_jobs", "kw_debug_reorder",
     "kw_debug_tile_descs", "kw_debug_tile_cost", "kw_debug_tile_slot", "kw_debug_sched_tail", "kw_debug_sched_rounds", "kw_debug_last_launches",
-    "kw_debug_last_kernels", "kw_debug_prod_shape", "kw_debug_plan_kernels",
+    "kw_debug_last_kernels", "kw_debug_prod_shape", "kw_debug_plan_kernels", "kw_debug_last_variants", "kw_debug_plan_variants",
+    "kw_debug_resolve_variant",
     "kw_batch_from_json", "kw_batch_from_soa", "kw_batch_view", "kw_batch_to_device", "kw_batch_to_device_async",
     "kw_stream_create", "kw_stream_destroy", "kw_validate_host", "kw_validate_host_packed", "kw_packed_word",
     "kw_packed_unpack", "kw_debug_pack_words", "kw_batch_summary", "kw_validate_host_summary", "kw_batch_verdict_rows",
@@ -195,6 +199,9 @@ def lib():
         "kw_debug_last_kernels": (ip, [vp, C.POINTER(u32), sz, C.POINTER(sz)]),
         "kw_debug_prod_shape": (ip, [u32, ip, u32, u32, ip, ip, u32, ip, ip]),
         "kw_debug_plan_kernels": (ip, [vp, vp, C.POINTER(i32), u32, ip, C.POINTER(u32), sz, C.POINTER(sz)]),
+        "kw_debug_last_variants": (ip, [vp, C.POINTER(u32), sz, C.POINTER(sz)]),
+        "kw_debug_plan_variants": (ip, [vp, vp, C.POINTER(i32), u32, ip, C.POINTER(u32), sz, C.POINTER(sz)]),
+        "kw_debug_resolve_variant": (u32, [u32]),
         "kw_debug_reorder": (ip, [vp, C.POINTER(u64), sz, C.POINTER(u64), C.POINTER(vp)]),
         "kw_batch_from_json": (ip, [C.POINTER(cp), C.POINTER(sz), sz, ip, C.POINTER(vp), C.POINTER(C.c_int64), cp, sz]),
         "kw_batch_from_soa": (ip, [C.POINTER(KwSoa), C.POINTER(vp)]),
