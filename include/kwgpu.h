@@ -621,6 +621,53 @@ int kw_batch_finding_key(const kw_batch *b, uint64_t row, uint32_t word, char *b
  * to the end, the findings the verify launch handed to the host (leftovers), the table's slots, and
  * the ranges that were cut. KW_E_ARG for a batch that was never digested. */
 int kw_debug_digest_stats(const kw_batch *b, uint64_t *out);
+/* The drill-down of the digest: the members of the groups a caller names, for the step between
+ * "what is wrong and how often" and the messages (tickets, labels, the per-resource entries of a
+ * policy report). Record g of `groups` names the group of the finding at (groups[g].first_row,
+ * groups[g].col): the pairs of that column with the same reason, the same KW_F_ALLOWED bit and a
+ * byte-equal key (the rules of kw_digest above). Only col, word and first_row are read: count is
+ * ignored, and first_row may be any member of the group, with word its word. All arrays caller-owned:
+ *   off    u64[ngroups + 1], required when ngroups > 0: off[g] .. off[g + 1] bound group g's members
+ *          in rows and words, in the order of the caller's list.
+ *   rows   u64[cap]: the members' batch rows (never device rows, also for a split batch), ascending
+ *          within a group; a group holds a row at most once (a group lives in one column and a pair
+ *          has one word).
+ *   words  u32[cap], or NULL for the rows only: the verdict word of (rows[i], the group's col), so
+ *          kw_format_response(env, b, rows[i], policy of col, words[i], ...) gives each member's exact
+ *          message with no further read-back.
+ *   n (output): the members of all named groups together.
+ * For the records of a digest of the same pass: off[g + 1] - off[g] = count, rows[off[g]] =
+ * first_row, words[off[g]] = word. When n > cap: KW_E_NOSPACE with n and all of off exact, the
+ * contents of rows and words then unspecified (as kw_digest treats cap). KW_E_ARG: col >= the pass's
+ * columns or first_row >= its rows; a word that is not a finding, or is a wide finding (those are
+ * listed in kw_digest.wide and belong to no group); a word that differs from the pass's word at
+ * (first_row, col), as a record of another pass does; two records that name the same group; off NULL
+ * with ngroups > 0; rows NULL with cap > 0. ngroups = 0 is KW_OK with n = 0. The same input gives the
+ * same bytes. No reference counterpart (an output form of a pass, as the packed, the summary and the
+ * digest forms). */
+typedef struct kw_members {
+  uint64_t *off;
+  uint64_t *rows;
+  uint32_t *words;
+  size_t cap;
+  size_t n;
+} kw_members;
+/* The members over the batch's last all-pairs device pass (kw_validate_batch or a bulk pass), found
+ * on the device over the words where they lie, as kw_batch_digest reads them: the named groups go
+ * into a selection table built on the host from the host batch's columns, one launch checks every
+ * record's word against the pass, one walk over the words probes the table for each finding whose
+ * (reason, allowed) class some named group of its column has and compares its key bytes with the
+ * representative's, so the result is exact whatever the hash does; only the per-group counts and
+ * the members come back, and the host orders them. Does not depend on KW_DIGEST_TABLE,
+ * KW_DIGEST_HASH_BITS or KW_SPLIT, nor on whether kw_batch_digest ran. Synchronises with the pass's
+ * stream as kw_batch_digest does. KW_E_ARG as above and, as for the digest, after kw_validate_rows,
+ * for a batch without a pass, for rows >= 2^32 and when a record's key column is not resident. A
+ * KW_E_ARG or KW_E_NOSPACE leaves the batch good for further calls. */
+int kw_batch_digest_members(kw_batch *b, const kw_digest_rec *groups, size_t ngroups, kw_members *out);
+/* Diagnostic (tests, documents): the same members from full words [rows][npol] (rows <= the batch's)
+ * and the host batch, by the reference reducer: an ordered map over the exact keys, no hashing. */
+int kw_debug_digest_members_words(const kw_batch *b, const uint32_t *words, uint64_t rows, uint32_t npol,
+                                  const kw_digest_rec *groups, size_t ngroups, kw_members *out);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes

@@ -290,4 +290,10 @@ inline const StrCol& host_str(const Batch& B, int m) {
 // The rows the device holds, in device order: the reordered copy of a split batch, else the batch.
 inline const Batch& dev_rows(const kw_batch* kb) { return kb->dev && kb->dev->dev_b ? *kb->dev->dev_b : kb->b; }
 
+// The columns a finding's key is cut from (digest.hpp digest_key; digest.cpp): the host batch's, in
+// batch rows, and the device copy's, in device rows, where a string column that is not resident
+// stays absent.
+DigestCols host_cols(const Batch& B);
+DigestCols device_cols(const kw_batch* kb);
+
 }  // namespace kw

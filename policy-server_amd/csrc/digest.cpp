@@ -31,7 +31,9 @@ struct Drain {
   ~Drain() { (void)hipStreamSynchronize(s); }
 };
 
-// The host batch's columns as the key function reads them (batch rows).
+}  // namespace
+
+// The host batch's columns as the key function reads them (batch rows; members.cpp reads them too).
 DigestCols host_cols(const Batch& B) {
   DigestCols C{};
   C.rows = B.n;
@@ -63,6 +65,8 @@ DigestCols device_cols(const kw_batch* kb) {
   }
   return C;
 }
+
+namespace {
 
 double ms_since(std::chrono::steady_clock::time_point t) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();

@@ -2537,6 +2537,105 @@ hipError_t launch_digest_gather(const DigestArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- the digest's drill-down (kernels.hpp MembersArgs, members.hpp) ---------------------------------
+
+__global__ void __launch_bounds__(256) members_check_kernel(MembersArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.nslots) return;
+  const MemberSlot sl = a.table[i];
+  if (sl.tag == 0u) return;
+  if (sl.rep_row >= a.cols.rows || sl.col >= a.npol || a.words[sl.rep_row * a.npol + sl.col] != sl.word)
+    __hip_atomic_store(&a.head->bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A lane's run of members of one group into the group's count.
+__device__ inline void members_flush(const MembersArgs& a, uint32_t group, uint64_t n) {
+  if (n) __hip_atomic_fetch_add(&a.counts[group], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(256) members_walk_kernel(MembersArgs a, PackGeom p) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, grp = blockIdx.y;
+  const uint32_t mycol = 64u * grp + lane % p.w;
+  // (a lane keeps a column for the whole launch: its mask of selected classes stays in a register)
+  const uint64_t cmask = (lane / p.w < p.ipi && mycol < a.npol) ? a.colmask[mycol] : 0ull;
+  if (!__ballot(cmask != 0ull)) return;  // wave-uniform: no named group lives in these columns
+  const uint64_t unit = digest_unit_rows(p), stride = (uint64_t)kDigestWaves * gridDim.x * unit;
+  uint32_t h_group = kMembersNone;
+  uint64_t h_n = 0;
+  for (uint64_t row0 = ((uint64_t)blockIdx.x * kDigestWaves + wave) * unit; row0 < a.cols.rows; row0 += stride) {  // wave-uniform
+    uint32_t x[kDigestRounds], sel[kDigestRounds];
+#pragma unroll
+    for (uint32_t t = 0; t < kDigestRounds; ++t) {
+      const DigestLane L = digest_lane(p, a.cols.rows, 0u, a.npol, grp, row0, t, lane);
+      x[t] = L.on ? __builtin_nontemporal_load(a.words + L.row * a.npol + L.col) : 0u;  // (0: no finding)
+    }
+    uint32_t mine = 0;  // this lane's members in the unit
+#pragma unroll
+    for (uint32_t t = 0; t < kDigestRounds; ++t) {
+      const uint32_t v = x[t];
+      sel[t] = kMembersNone;
+      if (digest_finding(v) && !digest_wide(v) && ((cmask >> members_class_bit(digest_class(v))) & 1ull) &&
+          !(digest_need(digest_kind(KW_REASON(v))) & ~a.loaded)) {
+        const DigestLane L = digest_lane(p, a.cols.rows, 0u, a.npol, grp, row0, t, lane);
+        sel[t] = members_find(a.table, a.nslots, a.cols, a.hash_bits, L.row, L.col, v);
+      }
+      mine += sel[t] != kMembersNone ? 1u : 0u;
+    }
+    if (!__ballot(mine != 0u)) continue;  // wave-uniform
+    // one add per wave for the unit's members: an inclusive scan of the lanes' counts, the last lane
+    // adds the total, every lane's members follow those of the lanes below it
+    uint32_t upto = mine;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t o = (uint32_t)__shfl_up((int)upto, d);
+      if (lane >= d) upto += o;
+    }
+    uint64_t base = 0;
+    if (lane == 63u) base = __hip_atomic_fetch_add(&a.head->nlist, (uint64_t)upto, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)base, 63), hi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), 63);
+    uint64_t at = (((uint64_t)hi << 32) | lo) + (upto - mine);
+#pragma unroll
+    for (uint32_t t = 0; t < kDigestRounds; ++t) {
+      const uint32_t group = sel[t];
+      if (group == kMembersNone) continue;
+      const DigestLane L = digest_lane(p, a.cols.rows, 0u, a.npol, grp, row0, t, lane);
+      if (at < a.list_cap) {
+        MemberEntry e;
+        e.key = member_key(group, a.d2b ? a.d2b[L.row] : L.row);
+        e.word = x[t];
+        e.pad = 0;
+        a.list[at] = e;
+      }
+      ++at;
+      if (group == h_group) {
+        ++h_n;
+      } else {
+        members_flush(a, h_group, h_n);
+        h_group = group;
+        h_n = 1;
+      }
+    }
+  }
+  members_flush(a, h_group, h_n);
+}
+
+hipError_t launch_members_check(const MembersArgs& a, hipStream_t s) {
+  if (a.nslots == 0 || (a.nslots & (a.nslots - 1u)) || a.nslots > (1ull << 33)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(members_check_kernel, dim3((uint32_t)((a.nslots + 255u) / 256u)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_members_walk(const MembersArgs& a, hipStream_t s) {
+  if (a.cols.rows == 0 || a.npol == 0) return hipSuccess;
+  if (a.nslots == 0 || (a.nslots & (a.nslots - 1u))) return hipErrorInvalidValue;
+  const uint64_t unit = digest_unit_rows(pack_geom(a.npol)), nunits = (a.cols.rows + unit - 1u) / unit;
+  const uint64_t want = (nunits + kDigestWaves - 1u) / kDigestWaves, most = (uint64_t)std::max<uint32_t>(device_cus(), 1u) * 8u;
+  const uint32_t gy = packed_groups(a.npol);
+  if (gy > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(members_walk_kernel, dim3((uint32_t)std::min(want, most), gy), dim3(256), 0, s, a, pack_geom(a.npol));
+  return hipGetLastError();
+}
+
 hipError_t launch_overflow(const EvalArgs& a, const TileArgs* d_t, const uint32_t* d_overflow, uint32_t n_overflow,
                            hipStream_t s) {
   if (n_overflow == 0 || a.nrows == 0) return hipSuccess;

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "digest.hpp"
+#include "members.hpp"
 #include "kwdev.hpp"
 #include "outcomes.hpp"
 #include "packed.hpp"
@@ -573,6 +574,40 @@ struct DigestArgs {
 hipError_t launch_digest_count(const DigestArgs& a, hipStream_t s);
 hipError_t launch_digest_verify(const DigestArgs& a, hipStream_t s);
 hipError_t launch_digest_gather(const DigestArgs& a, hipStream_t s);
+
+// The digest's drill-down (kw_batch_digest_members; the table, the probe and the order: members.hpp):
+// two launches over the verdict words, none waiting on another workgroup.
+//   check    one thread per slot of the selection table: a slot that names a group compares the
+//            pass's word at its representative with the record's word and raises head->bad when they
+//            differ (a record of another pass). Per slot and not per record, so the table is all the
+//            device needs of the record list.
+//   walk     the words walked with the digest's geometry (digest_lane: a lane keeps a column, grid.y
+//            the column groups of 64, a unit's loads in flight before the first is used). A lane
+//            holds its column's mask of selected classes in a register: a finding of another class
+//            never touches its key bytes, and a wave none of whose columns has a named group leaves
+//            at once. A finding that passes hashes its key and probes (members_find). The members of
+//            a unit take their places in the list through one add per wave (a scan of the lanes'
+//            counts, one lane adds the total), and write (group, batch row, word) while the place is
+//            below list_cap; a lane's run of members of one group adds to that group's count once.
+//            Counting goes on past list_cap, so the counts stay exact.
+// Relaxed agent-scope vector atomics and plain vector stores only, no LDS; the stream orders the
+// launches, the zeroing before and the read-back after. Integer adds: the counts do not depend on
+// the order in which the waves arrive, the list's order does (the host sorts it).
+struct MembersArgs {
+  const uint32_t* words;    // [rows][npol], device-row order
+  DigestCols cols;          // the device columns (device rows)
+  const uint32_t* d2b;      // the batch row of each device row, nullptr: the same
+  const MemberSlot* table;  // [nslots], rep_row in device rows
+  const uint64_t* colmask;  // [npol] members_class_bit masks
+  uint64_t* counts;         // [ngroups], added to
+  MemberEntry* list;        // [max(list_cap, 1)]
+  MembersHead* head;
+  uint64_t nslots, list_cap;
+  uint32_t hash_bits, npol;
+  uint32_t loaded;          // string columns (bits of Str) that are resident
+};
+hipError_t launch_members_check(const MembersArgs& a, hipStream_t s);
+hipError_t launch_members_walk(const MembersArgs& a, hipStream_t s);
 
 hipError_t launch_nfa_classify(const EvalArgs& a, const TileArgs* d_t, const NfaPass& np, uint32_t threads, hipStream_t s);
 // threads of the NFA pass's grid for `items` entities within a scratch budget

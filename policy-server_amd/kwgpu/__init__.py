@@ -475,6 +475,18 @@ DIGEST_REC = [("col", "<u4"), ("word", "<u4"), ("first_row", "<u8"), ("count", "
 Digest = collections.namedtuple("Digest", ["recs", "wide", "findings"])
 
 
+class MembersNoSpace(NoSpace):
+    """KW_E_NOSPACE of a digest drill-down: .need members are required; .off holds the exact bounds."""
+
+    def __init__(self, need, off):
+        Exception.__init__(self, f"the named groups have {need} members")
+        self.need, self.off = int(need), off
+
+
+# off uint64 [groups + 1], rows uint64 [n] (batch rows), words uint32 [n] or None
+Members = collections.namedtuple("Members", ["off", "rows", "words"])
+
+
 class Batch:
     """A micro-batch of requests in SoA form (kw_batch)."""
 
@@ -756,6 +768,51 @@ class Batch:
         grow = cap is None and wide_cap is None
         return self._digest_call(lambda st: self._L.kw_debug_digest_words(self._h, ptr, rows, npol, st),
                                  4096 if cap is None else cap, 1024 if wide_cap is None else wide_cap, grow)
+
+    @staticmethod
+    def _members_call(call, recs, words, cap):
+        """call(record pointer, count, struct) into arrays of `cap` members: sized by the records'
+        counts when they are all non-zero, else grown once to the reported need; a `cap` that is given
+        and too small raises MembersNoSpace."""
+        import numpy as np
+        recs = np.ascontiguousarray(recs, dtype=np.dtype(DIGEST_REC)).reshape(-1)
+        ptr = recs.ctypes.data_as(C.POINTER(N.KwDigestRec))
+        grow = cap is None
+        if grow:
+            cap = int(recs["count"].sum()) if recs.size and (recs["count"] != 0).all() else 0
+        off = np.zeros(recs.size + 1, dtype=np.uint64)
+        for attempt in (0, 1):
+            rows = np.zeros(max(cap, 1), dtype=np.uint64)
+            wd = np.zeros(max(cap, 1), dtype=np.uint32) if words else None
+            st = N.KwMembers(off.ctypes.data_as(C.POINTER(C.c_uint64)), rows.ctypes.data_as(C.POINTER(C.c_uint64)),
+                             wd.ctypes.data_as(C.POINTER(C.c_uint32)) if words else None, cap, 0)
+            rc = call(ptr, recs.size, C.byref(st))
+            if rc != N.KW_E_NOSPACE:
+                break
+            if not grow or attempt:
+                raise MembersNoSpace(st.n, off)
+            cap = st.n
+        raise_for(rc, "the digest's members failed")
+        return Members(off, rows[:st.n], wd[:st.n] if words else None)
+
+    def digest_members(self, recs, words=True, cap=None):
+        """The members of the digest groups `recs` names (kw_batch_digest_members), found on the
+        device over the last all-pairs pass: Members(off, rows, words) with off[g] .. off[g + 1]
+        bounding group g's batch rows (ascending) and their verdict words, in the order of `recs` (a
+        structured array as Digest.recs; col, word and first_row are read). The arrays are sized by
+        recs["count"].sum() when every count is non-zero and grow once to the reported need otherwise;
+        with `cap` a selection that needs more raises MembersNoSpace (.need, .off)."""
+        return self._members_call(lambda p, n, st: self._L.kw_batch_digest_members(self._h, p, n, st), recs, words, cap)
+
+    def digest_members_from_words(self, words, npol, recs, with_words=True, cap=None):
+        """Diagnostic (kw_debug_digest_members_words): the same members from full words [rows][npol]
+        over this batch's host columns, by the reference reducer (an ordered map over the exact keys)."""
+        import numpy as np
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        nrows = words.size // npol
+        wp = words.ctypes.data_as(C.POINTER(C.c_uint32))
+        return self._members_call(lambda p, n, st: self._L.kw_debug_digest_members_words(self._h, wp, nrows, npol, p, n, st),
+                                  recs, with_words, cap)
 
     def finding_key(self, row, word):
         """The key bytes of the finding `word` at batch row `row` (kw_batch_finding_key), host only:

@@ -120,6 +120,12 @@ class KwDigest(C.Structure):
                 ("findings", C.c_uint64)]
 
 
+class KwMembers(C.Structure):
+    """kw_members: the members of named digest groups (include/kwgpu.h)."""
+    _fields_ = [("off", C.POINTER(C.c_uint64)), ("rows", C.POINTER(C.c_uint64)), ("words", C.POINTER(C.c_uint32)),
+                ("cap", C.c_size_t), ("n", C.c_size_t)]
+
+
 EXPORTS = [
     "kw_env_build", "kw_env_build_yaml", "kw_yaml_to_json", "kw_env_serialize", "kw_env_deserialize", "kw_env_destroy", "kw_env_lookup",
     "kw_env_policy_count", "kw_env_policy_id", "kw_env_is_group", "kw_env_get_policy_mode",
@@ -136,6 +142,7 @@ EXPORTS = [
     "kw_batch_last_pass",
     "kw_debug_summarize_words", "kw_batch_outcomes", "kw_debug_outcome_words", "kw_batch_attribute_groups",
     "kw_batch_digest", "kw_debug_digest_words", "kw_batch_finding_key", "kw_debug_digest_stats",
+    "kw_batch_digest_members", "kw_debug_digest_members_words",
     "kw_metrics_add_outcomes", "kw_metrics_record_pass", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
     "kw_batch_destroy", "kw_debug_host_walk", "kw_validate_batch", "kw_validate_rows", "kw_batch_verdicts",
     "kw_validate_timed", "kw_format_response", "kw_format_response_doc", "kw_env_group_members", "kw_evaluate",
@@ -231,6 +238,8 @@ def lib():
         "kw_debug_digest_words": (ip, [vp, C.POINTER(u32), u64, u32, C.POINTER(KwDigest)]),
         "kw_batch_finding_key": (ip, [vp, u64, u32, cp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "kw_debug_digest_stats": (ip, [vp, C.POINTER(u64)]),
+        "kw_batch_digest_members": (ip, [vp, C.POINTER(KwDigestRec), sz, C.POINTER(KwMembers)]),
+        "kw_debug_digest_members_words": (ip, [vp, C.POINTER(u32), u64, u32, C.POINTER(KwDigestRec), sz, C.POINTER(KwMembers)]),
         "kw_metrics_add_outcomes": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64, C.POINTER(u64), u32, C.POINTER(u64)]),
         "kw_metrics_record_pass": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64]),
         "kw_batch_pin_host": (ip, [vp, ip]),
