@@ -668,6 +668,60 @@ int kw_batch_digest_members(kw_batch *b, const kw_digest_rec *groups, size_t ngr
  * and the host batch, by the reference reducer: an ordered map over the exact keys, no hashing. */
 int kw_debug_digest_members_words(const kw_batch *b, const uint32_t *words, uint64_t rows, uint32_t npol,
                                   const kw_digest_rec *groups, size_t ngroups, kw_members *out);
+/* The last step of the audit flow on the device: the messages of chosen findings. The message of
+ * item i, the pair (rows[i], cols[i]) of the batch's last all-pairs device pass, is the byte string
+ * kw_format_response puts into status.message for a plain policy: the policy's own text for the
+ * pass's word at that pair (its KW_REASON and KW_ARG), raw UTF-8 with no JSON escaping, whatever
+ * mode, bypass or constraints made of the word (the digest counts a finding that was let through in
+ * the same way). A word of reason 0, or of a reason no product word has, has the empty message.
+ * `policies` [npol] is the policy list of that pass: the batch does not record the list of every
+ * kind of pass, so it is the caller's contract, as the policy argument of kw_format_response is;
+ * only its length is checked against the pass. All arrays caller-owned:
+ *   off    u64[n + 1], required when n > 0: message i is text[off[i] .. off[i + 1]).
+ *   text   cap bytes; page-locked memory (kw_host_alloc) is written by direct DMA, pageable memory
+ *          through pinned bounce blocks.
+ *   bytes  (output) off[n].
+ *   words  u32[n] or NULL: the pass's word of each item.
+ *   host   u64[host_cap]: the indices i, ascending, of the items the device does not render. They
+ *          have a zero-length message here and are left to kw_format_response: reason
+ *          KW_R_GROUP_EXPR (its text may be replaced by a data-dependent one), a word of reason 1-12
+ *          whose ARG is KW_ARG_WIDE (its argument is in the pass's side data), and a word whose
+ *          argument the request does not hold (no product word). nhost (output): their number.
+ * Items are in the caller's order; any order and repeats are allowed; rows are batch rows, never
+ * device rows, also for a split batch. When bytes > cap or nhost > host_cap: KW_E_NOSPACE with bytes,
+ * nhost and all of off exact, text and host then unspecified (as kw_members treats cap). KW_E_ARG: a
+ * row or col outside the pass; npol other than the pass's words per row; a batch without a pass; a
+ * pass of kw_validate_rows; a policy index outside the env's visible policies; a message that quotes
+ * a string column that is not resident; off NULL with n > 0; text NULL with cap > 0; host NULL with
+ * host_cap > 0. n = 0 is KW_OK. The same input gives the same bytes. A KW_E_ARG or KW_E_NOSPACE
+ * leaves the batch good for further calls. The container names, which no pass reads, are uploaded
+ * from the host batch by the first call and kept until the batch is uploaded again or destroyed.
+ * The items run in rounds of at most KW_MESSAGES_CHUNK; a round's lengths, their scan and the text
+ * are three steps on the device, the text written through windows of KW_MESSAGES_WINDOW bytes. Synchronises
+ * with the pass's stream. No reference counterpart (an output form of a pass). */
+typedef struct kw_messages {
+  uint64_t *off;
+  char *text;
+  size_t cap;
+  size_t bytes;
+  uint32_t *words;
+  uint64_t *host;
+  size_t host_cap, nhost;
+} kw_messages;
+int kw_batch_messages(kw_batch *b, const kw_env *env, const int32_t *policies, uint32_t npol,
+                      const uint64_t *rows, const uint32_t *cols, size_t n, kw_messages *out);
+/* Diagnostic (tests, documents): the same output on the host from full words [nrows][npol] (nrows <=
+ * the batch's) and the host batch. how = 0: one policy_message call per item, the reference (an item
+ * whose argument the request does not hold is listed in host instead of failing the call); how = 1:
+ * the piece renderer the device runs (csrc/messages.hpp), over the host columns. */
+int kw_debug_messages_words(const kw_env *env, const kw_batch *b, const int32_t *policies, uint32_t npol,
+                            const uint32_t *words, uint64_t nrows, const uint64_t *rows,
+                            const uint32_t *cols, size_t n, int how, kw_messages *out);
+/* Diagnostic (tests): what the batch's last kw_batch_messages did. out[0..5): the rounds, the
+ * staging windows written, the messages that spanned more than one window, the items listed for the
+ * host, and whether that call uploaded the container names (1 / 0). KW_E_ARG for a batch that never
+ * ran the call. */
+int kw_debug_messages_stats(const kw_batch *b, uint64_t *out);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes

@@ -209,6 +209,16 @@ struct DeviceBatch {
   // the last kw_batch_digest (kw_debug_digest_stats): ranges run, leftovers, table slots, ranges cut
   bool digest_ran = false;
   uint64_t digest_stats[4] = {0, 0, 0, 0};
+  // the container names (kw_batch_messages uploads them on first use: no pass reads them), in the
+  // device's container order: one block [offsets | bytes and their zero tail], kept while this
+  // device copy lives
+  uint8_t* names = nullptr;
+  size_t names_bytes = 0;
+  DCol name_col;
+  // the last kw_batch_messages (kw_debug_messages_stats): rounds, windows written, messages that
+  // spanned a window, items left to the host, whether it uploaded the names
+  bool messages_ran = false;
+  uint64_t messages_stats[5] = {0, 0, 0, 0, 0};
   // tile capacities of this batch (plan_pass), per tile height tried
   struct RowsPlan {
     uint32_t rows = 0;
@@ -233,6 +243,7 @@ struct DeviceBatch {
     P.release(device, desc, desc_cap * sizeof(TileDesc));
     P.release(device, overflow, overflow_cap * 4);
     P.release(device, cols, cols_bytes);
+    P.release(device, names, names_bytes);
     P.release(device, verdicts, verdict_cap * 4);
     P.release(device, g_cls, g_cls_cap * 2);
     P.release(device, nfa_cls, nfa_cls_cap * 2);

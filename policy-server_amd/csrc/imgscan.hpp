@@ -13,6 +13,12 @@
 #define KW_XAD 1
 #endif
 
+#if defined(__clang__)  // (hipcc and clang unroll; a host compiler that does not know the pragma stays quiet)
+#define KW_UNROLL _Pragma("unroll")
+#else
+#define KW_UNROLL
+#endif
+
 namespace kw {
 
 KW_HD inline uint32_t align_bytes(uint32_t hi, uint32_t lo, uint32_t sh) {
@@ -33,7 +39,7 @@ constexpr char kLocalhost[] = "localhost";
 template <int N>
 KW_HD inline bool equals_const(const uint8_t* __restrict__ bytes, uint32_t b, uint32_t e, const char (&s)[N]) {
   if ((int)(e - b) != N - 1) return false;
-#pragma unroll
+  KW_UNROLL
   for (int i = 0; i < N - 1; ++i)
     if (bytes[b + (uint32_t)i] != (uint8_t)s[i]) return false;
   return true;

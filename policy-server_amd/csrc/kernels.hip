@@ -2636,6 +2636,177 @@ hipError_t launch_members_walk(const MembersArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- the messages of chosen findings (kernels.hpp MessagesArgs, messages.hpp) -----------------------
+
+__global__ void __launch_bounds__(256) messages_len_kernel(MessagesArgs a) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  const uint64_t row = a.drow[i];
+  const uint32_t col = a.col[i];
+  uint32_t word = 0, st = MSG_TEXT;
+  MsgPlan P;
+  P.npc = 0;
+  P.len = 0;
+  if (row < a.cols.c.rows && col < a.npol) {  // (the host checked both: nothing is read outside the pass)
+    word = a.words[row * a.npol + col];
+    st = message_pieces(a.cols, msg_settings(a.settings), row, col, word, &P);
+  }
+  a.len[i] = st == MSG_TEXT ? P.len : 0u;
+  a.mark[i] = st == MSG_HOST ? 1u : 0u;
+  if (a.out_words) a.out_words[i] = word;
+  if (st == MSG_MISSING) __hip_atomic_store(&a.head->missing, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ inline uint64_t msg_shfl_up(uint64_t v, uint32_t d) {
+  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// The exclusive prefix of `mine` among the workgroup's threads and the workgroup's total: a wave scan
+// by shuffles, the waves' totals through LDS. Every thread calls it; it ends in a barrier, so
+// wave_sum may be used again at once.
+__device__ inline uint64_t msg_block_scan(uint64_t mine, uint64_t* wave_sum, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint64_t upto = mine;
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint64_t o = msg_shfl_up(upto, d);
+    if (lane >= d) upto += o;
+  }
+  if (lane == 63u) wave_sum[wave] = upto;
+  __syncthreads();
+  uint64_t before = 0, all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kMsgScanThreads / 64u; ++w) {
+    const uint64_t s = wave_sum[w];
+    before += w < wave ? s : 0ull;
+    all += s;
+  }
+  __syncthreads();
+  *total = all;
+  return before + (upto - mine);
+}
+
+// sums: a workgroup a tile of kMsgScanTile lengths, its total into sums[tile].
+__global__ void __launch_bounds__(kMsgScanThreads) messages_sums_kernel(MessagesArgs a) {
+  __shared__ uint64_t wave_sum[kMsgScanThreads / 64u];
+  const uint32_t i = blockIdx.x * kMsgScanTile + 4u * threadIdx.x;
+  uint64_t mine = 0, total;
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; ++j) mine += i + j < a.n ? a.len[i + j] : 0u;
+  (void)msg_block_scan(mine, wave_sum, &total);
+  if (threadIdx.x == 0u) a.sums[blockIdx.x] = total;
+}
+
+// bases: one workgroup turns the tiles' totals into their bases (base + the totals before), in
+// place, and writes the round's end into off[n].
+__global__ void __launch_bounds__(kMsgScanThreads) messages_bases_kernel(MessagesArgs a) {
+  __shared__ uint64_t wave_sum[kMsgScanThreads / 64u];
+  const uint32_t nt = (a.n + kMsgScanTile - 1u) / kMsgScanTile;
+  uint64_t carry = a.base;  // (every thread keeps the same running total)
+  for (uint32_t t0 = 0; t0 < nt; t0 += kMsgScanTile) {  // uniform
+    const uint32_t i = t0 + 4u * threadIdx.x;
+    uint64_t l[4], total;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) l[j] = i + j < nt ? a.sums[i + j] : 0ull;
+    uint64_t at = carry + msg_block_scan(l[0] + l[1] + l[2] + l[3], wave_sum, &total);
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+      if (i + j < nt) a.sums[i + j] = at;
+      at += l[j];
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0u) a.off[a.n] = carry;
+}
+
+// scan: a workgroup a tile again, its offsets from the tile's base.
+__global__ void __launch_bounds__(kMsgScanThreads) messages_scan_kernel(MessagesArgs a) {
+  __shared__ uint64_t wave_sum[kMsgScanThreads / 64u];
+  const uint32_t i = blockIdx.x * kMsgScanTile + 4u * threadIdx.x;
+  uint32_t l[4];
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; ++j) l[j] = i + j < a.n ? a.len[i + j] : 0u;
+  uint64_t total;
+  uint64_t at = a.sums[blockIdx.x] + msg_block_scan((uint64_t)l[0] + l[1] + l[2] + l[3], wave_sum, &total);
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; ++j) {
+    if (i + j < a.n) a.off[i + j] = at;
+    at += l[j];
+  }
+}
+
+extern __shared__ uint4 messages_window[];
+
+__global__ void __launch_bounds__(64) messages_write_kernel(MessagesArgs a) {
+  const uint32_t lane = threadIdx.x, i0 = blockIdx.x * kMsgWaveItems, i = i0 + lane;
+  const uint32_t i1 = i0 + kMsgWaveItems < a.n ? i0 + kMsgWaveItems : a.n;
+  const uint64_t rb = a.off[i0], re = a.off[i1];  // the wave's byte range
+  if (re <= rb) return;                           // uniform: 64 empty messages
+  MsgPlan P;
+  P.npc = 0;
+  P.len = 0;
+  uint64_t mb = rb;
+  if (i < a.n) {
+    mb = a.off[i];
+    const uint64_t row = a.drow[i];
+    const uint32_t col = a.col[i];
+    if (row < a.cols.c.rows && col < a.npol &&
+        message_pieces(a.cols, msg_settings(a.settings), row, col, a.words[row * a.npol + col], &P) != MSG_TEXT) {
+      P.npc = 0;
+      P.len = 0;
+    }
+    if ((uint64_t)P.len != a.off[i + 1] - mb) {  // (not the message the lengths were counted from: nothing is copied)
+      P.npc = 0;
+      P.len = 0;
+    }
+  }
+  uint8_t* lds = (uint8_t*)messages_window;
+  const uint64_t w0 = rb & ~(uint64_t)15u;
+  uint64_t nwin = 0;
+  for (uint64_t wb = w0; wb < re; wb += a.window, ++nwin) {  // uniform
+    uint32_t skip, at, n;
+    msg_clip(mb, P.len, wb, a.window, &skip, &at, &n);
+    if (n) msg_copy_window(P, skip, n, lds + at);
+    __syncthreads();  // one wave: the LDS writes are done before any lane reads the window
+    const uint64_t lo = wb > rb ? wb : rb, hi = wb + a.window < re ? wb + a.window : re;
+    uint64_t body, tail;
+    msg_chunks(lo, hi, &body, &tail);
+    for (uint64_t g = lo + lane; g < body; g += 64u) a.text[g - a.text_base] = lds[g - wb];
+    for (uint64_t g = body + 16u * lane; g < tail; g += 16u * 64u)
+      *(uint4*)(a.text + (g - a.text_base)) = *(const uint4*)(lds + (g - wb));
+    for (uint64_t g = tail + lane; g < hi; g += 64u) a.text[g - a.text_base] = lds[g - wb];
+    __syncthreads();  // the window is read before the next one is filled
+  }
+  const uint64_t span = __popcll(__ballot(msg_windows_of(mb, P.len, w0, a.window) > 1u));
+  if (lane == 0u) {
+    __hip_atomic_fetch_add(&a.head->windows, nwin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (span) __hip_atomic_fetch_add(&a.head->spanning, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+hipError_t launch_messages_len(const MessagesArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(messages_len_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_messages_scan(const MessagesArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  const uint32_t tiles = (a.n + kMsgScanTile - 1u) / kMsgScanTile;
+  hipLaunchKernelGGL(messages_sums_kernel, dim3(tiles), dim3(kMsgScanThreads), 0, s, a);
+  hipLaunchKernelGGL(messages_bases_kernel, dim3(1), dim3(kMsgScanThreads), 0, s, a);
+  hipLaunchKernelGGL(messages_scan_kernel, dim3(tiles), dim3(kMsgScanThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_messages_write(const MessagesArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  if (a.window < kMsgMinWindow || a.window > kMsgMaxWindow || (a.window & 15u) || (a.text_base & 15u)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(messages_write_kernel, dim3((a.n + kMsgWaveItems - 1u) / kMsgWaveItems), dim3(64), a.window, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_overflow(const EvalArgs& a, const TileArgs* d_t, const uint32_t* d_overflow, uint32_t n_overflow,
                            hipStream_t s) {
   if (n_overflow == 0 || a.nrows == 0) return hipSuccess;

@@ -6,6 +6,7 @@
 
 #include "digest.hpp"
 #include "members.hpp"
+#include "messages.hpp"
 #include "kwdev.hpp"
 #include "outcomes.hpp"
 #include "packed.hpp"
@@ -608,6 +609,50 @@ struct MembersArgs {
 };
 hipError_t launch_members_check(const MembersArgs& a, hipStream_t s);
 hipError_t launch_members_walk(const MembersArgs& a, hipStream_t s);
+
+// The messages of chosen findings (kw_batch_messages; the pieces, the windows and the settings
+// table: messages.hpp): three steps over one round of n items, ordered by the stream.
+//   len      one lane per item: the pass's word at (device row, col), message_pieces, the length,
+//            the word when asked for, the mark of an item left to the host; a message that quotes a
+//            column that is not resident raises head->missing.
+//   scan     the exclusive scan of the lengths into off[i] = base + the lengths before i (u64),
+//            off[n] the round's end, in the pack kernels' three steps: sums (a workgroup a tile of
+//            kMsgScanTile lengths, its total), bases (one workgroup scans the tiles' totals in
+//            place), scan (a workgroup a tile again, from its base); wave scans by shuffles, the
+//            waves' totals through LDS. One workgroup over all lengths took 6.9 ms for 11.6 M items
+//            (profiles/r16_messages.txt).
+//   write    a workgroup of one wave owns 64 consecutive items, so its output is one contiguous byte
+//            range. It walks the range in windows of `window` bytes of LDS that start at multiples
+//            of 16: each lane runs message_pieces again and copies the part of its message inside
+//            the window (msg_clip, msg_copy_window: LDS byte and dword writes); after the barrier
+//            the wave stores the window with aligned 16-byte global stores, the range's unaligned
+//            head and tail in single bytes, and nothing outside [off[i0], off[i0 + 64)). Byte g of
+//            the call's text lies at text[g - text_base], text_base a multiple of 16.
+// Plain vector loads and stores and relaxed agent-scope vector atomics (the counters of head) only.
+struct MessagesHead {
+  uint64_t windows, spanning;  // windows written; messages that touched more than one
+  uint32_t missing, pad;
+};
+constexpr uint32_t kMsgScanThreads = 1024, kMsgScanTile = 4096;
+struct MessagesArgs {
+  const uint32_t* words;    // [rows][npol], device-row order
+  MsgCols cols;             // the device columns (device rows) and the container names
+  const uint8_t* settings;  // the pass's settings table (msg_settings)
+  const uint32_t* drow;     // [n] device rows
+  const uint32_t* col;      // [n]
+  uint32_t* len;            // [n]
+  uint32_t* out_words;      // [n] or nullptr
+  uint8_t* mark;            // [n] 1: left to the host
+  uint64_t* off;            // [n + 1]
+  uint64_t* sums;           // [ceil(n / kMsgScanTile)]: the tiles' totals, then their bases
+  uint8_t* text;
+  MessagesHead* head;
+  uint64_t base, text_base;
+  uint32_t n, npol, window;
+};
+hipError_t launch_messages_len(const MessagesArgs& a, hipStream_t s);
+hipError_t launch_messages_scan(const MessagesArgs& a, hipStream_t s);
+hipError_t launch_messages_write(const MessagesArgs& a, hipStream_t s);
 
 hipError_t launch_nfa_classify(const EvalArgs& a, const TileArgs* d_t, const NfaPass& np, uint32_t threads, hipStream_t s);
 // threads of the NFA pass's grid for `items` entities within a scratch budget

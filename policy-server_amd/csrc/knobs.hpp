@@ -21,7 +21,7 @@ enum Knob : int {
   KW_SCHED, KW_SCHED_TAIL, KW_SPLIT, KW_GROUP_FORM, KW_POISON_VERDICTS, KW_FLATTEN_THREADS,
   KW_SLOT_ROWS, KW_HEAVY_ROWS, KW_HEAVY_CTR, KW_GLOBAL_TABLES, KW_TILE_SPLIT, KW_ROUND_SPLIT,
   KW_TILE_QUANTILE, KW_TILE_DEBUG, KW_TILE_CUT, KW_OUTCOME_TABLE, KW_TILE_GENERIC,
-  KW_DIGEST_TABLE, KW_DIGEST_HASH_BITS,
+  KW_DIGEST_TABLE, KW_DIGEST_HASH_BITS, KW_MESSAGES_CHUNK, KW_MESSAGES_WINDOW,
   KW_NKNOBS
 };
 
@@ -90,6 +90,8 @@ constexpr KnobRow kKnobs[KW_NKNOBS] = {
     knob_flag("KW_TILE_GENERIC", KnobKind::Off, kLive, kPlans, "every tile launch on the generic kernel, none on a production-shape one"),
     knob_int("KW_DIGEST_TABLE", kLive, kNoPlan, 64 << 20, 1, INT_MAX, kClamp, "kw_batch_digest: bytes of the device hash table (more groups are reduced in column ranges)"),
     knob_int("KW_DIGEST_HASH_BITS", kLive, kNoPlan, 64, 0, 64, kClamp, "kw_batch_digest: low bits of the key hash that are kept (tests: fewer make every probe collide)"),
+    knob_int("KW_MESSAGES_CHUNK", kLive, kNoPlan, 1 << 20, 1, 1 << 24, kClamp, "kw_batch_messages: items of one round (the device scratch is sized by it)"),
+    knob_int("KW_MESSAGES_WINDOW", kLive, kNoPlan, 4096, 256, 32768, kClamp, "kw_batch_messages: bytes of the LDS window a wave writes its text through (a multiple of 16)"),
 };
 
 constexpr bool knob_name_is(const char* a, const char* b) {
@@ -104,7 +106,7 @@ KW_KNOB_ROW(KW_SCHED); KW_KNOB_ROW(KW_SCHED_TAIL); KW_KNOB_ROW(KW_SPLIT); KW_KNO
 KW_KNOB_ROW(KW_FLATTEN_THREADS); KW_KNOB_ROW(KW_SLOT_ROWS); KW_KNOB_ROW(KW_HEAVY_ROWS); KW_KNOB_ROW(KW_HEAVY_CTR);
 KW_KNOB_ROW(KW_GLOBAL_TABLES); KW_KNOB_ROW(KW_TILE_SPLIT); KW_KNOB_ROW(KW_ROUND_SPLIT); KW_KNOB_ROW(KW_TILE_QUANTILE);
 KW_KNOB_ROW(KW_TILE_DEBUG); KW_KNOB_ROW(KW_TILE_CUT); KW_KNOB_ROW(KW_OUTCOME_TABLE); KW_KNOB_ROW(KW_TILE_GENERIC);
-KW_KNOB_ROW(KW_DIGEST_TABLE); KW_KNOB_ROW(KW_DIGEST_HASH_BITS);
+KW_KNOB_ROW(KW_DIGEST_TABLE); KW_KNOB_ROW(KW_DIGEST_HASH_BITS); KW_KNOB_ROW(KW_MESSAGES_CHUNK); KW_KNOB_ROW(KW_MESSAGES_WINDOW);
 #undef KW_KNOB_ROW
 
 // The plan cache's key for the KW_* settings (tests switch them between passes): the current

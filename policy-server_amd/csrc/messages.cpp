@@ -1,0 +1,361 @@
+// messages.cpp — the messages of chosen findings on a resident pass (include/kwgpu.h):
+// kw_batch_messages builds the pass's settings table from (env, policies), uploads the container
+// names on first use, and runs the items in rounds: the lengths, their scan and the text are three
+// steps a round, the offsets, the words and the host marks come back through a pooled block, the
+// text by direct DMA into page-locked memory or through a bounce block. The steps of a round run
+// serially on the pass's stream (the next round's base is the total the host reads back). The two
+// host renderers of the diagnostic. The arithmetic is messages.hpp's, the kernels kernels.hip's.
+#include "messages.hpp"
+
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "devbatch.hpp"
+#include "kernels.hpp"
+#include "knobs.hpp"
+#include "pass.hpp"
+#include "service.hpp"
+#include "upload.hpp"
+
+namespace kw {
+namespace {
+
+static_assert(sizeof(MsgCol) == 44 && sizeof(MsgCons) == 16 && sizeof(MsgHead) == 16 && sizeof(MessagesHead) == 24, "messages records");
+
+// Declared after the leases a call holds: the stream is drained before any block returns to its pool,
+// on the error returns too.
+struct Drain {
+  hipStream_t s;
+  ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
+double ms_since(std::chrono::steady_clock::time_point t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+size_t up256(size_t n) { return (n + 255u) & ~(size_t)255u; }
+constexpr size_t kTask = 1u << 16;  // items of one staging task of the host workers
+
+// The settings table of a pass over `policies` (msg_build_table); KW_E_ARG for an index outside the
+// visible policies.
+int settings_table(const Env& E, const int32_t* policies, uint32_t npol, std::vector<uint64_t>* block) {
+  if (npol && !policies) return KW_E_ARG;
+  std::vector<MsgColSource> cols(npol);
+  for (uint32_t c = 0; c < npol; ++c) {
+    if (policies[c] < 0 || (size_t)policies[c] >= E.nvisible) return KW_E_ARG;
+    const PolicyRec& P = E.pol[(size_t)policies[c]];
+    MsgColSource& s = cols[c];
+    s.family = P.family;
+    s.ns = P.lists[0].empty() ? std::string() : P.lists[0][0];
+    s.message = P.message;
+    s.init = P.init_message;
+    s.mandatory = P.lists[1];
+    s.keys = P.lists[2];
+    s.regexes = P.lists[3];
+  }
+  *block = msg_build_table(cols);
+  return KW_OK;
+}
+
+bool out_ok(const kw_messages* out, const uint64_t* rows, const uint32_t* cols, size_t n) {
+  if (!out) return false;
+  if (n && (!rows || !cols || !out->off)) return false;
+  return !(out->cap && !out->text) && !(out->host_cap && !out->host);
+}
+
+// The host columns with the container names.
+MsgCols host_msg_cols(const Batch& B) {
+  MsgCols C;
+  C.c = host_cols(B);
+  C.name = DigestStr{B.ctr_name.off.data(), B.ctr_name.bytes.data(), B.ctr_name.n()};
+  return C;
+}
+
+// The container names to the device, in the device's container order (a split batch: the rows'
+// containers through the upload's row permutation), with the zero tail the other pools have.
+int upload_names(kw_batch* kb, hipStream_t s) {
+  DeviceBatch& D = *kb->dev;
+  const Batch& B = kb->b;
+  const StrCol& N = B.ctr_name;
+  const uint64_t nc = B.containers();
+  if (N.n() != nc) return KW_E_ARG;
+  const size_t b_off = up256((size_t)(nc + 1) * 4), b_bytes = up256((size_t)N.off.back() + 32), total = b_off + b_bytes;
+  BlockLease h;
+  HIPCHK(h.alloc(host_pool(), D.device, total));
+  uint32_t* off = (uint32_t*)h.p;
+  uint8_t* bytes = (uint8_t*)h.p + b_off;
+  memset(bytes, 0, b_bytes);
+  if (D.split && D.perm.size() == B.n) {
+    uint64_t e = 0;
+    off[0] = 0;
+    for (uint64_t d = 0; d < B.n; ++d) {
+      const uint64_t r = D.perm[d];
+      for (uint32_t c = B.ctr_off[r]; c < B.ctr_off[r + 1]; ++c, ++e) {
+        const uint32_t len = N.off[c + 1] - N.off[c];
+        memcpy(bytes + off[e], N.bytes.data() + N.off[c], len);
+        off[e + 1] = off[e] + len;
+      }
+    }
+    if (e != nc) return KW_E_ENGINE;
+  } else {
+    memcpy(off, N.off.data(), (size_t)(nc + 1) * 4);
+    if (N.off.back()) memcpy(bytes, N.bytes.data(), N.off.back());
+  }
+  void* d = nullptr;
+  HIPCHK(dev_pool().alloc(D.device, total, &d));
+  const hipError_t e1 = hipMemcpyAsync(d, h.p, total, hipMemcpyHostToDevice, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // (the staging block returns to its pool below)
+  if (e1 != hipSuccess || e2 != hipSuccess) {
+    dev_pool().release(D.device, d, total);
+    return KW_E_DEVICE;
+  }
+  D.names = (uint8_t*)d;
+  D.names_bytes = total;
+  D.name_col.off = (const uint32_t*)D.names;
+  D.name_col.bytes = D.names + b_off;
+  D.name_col.n = nc;
+  D.name_col.nbytes = N.off.back();
+  return KW_OK;
+}
+
+}  // namespace
+
+int batch_messages(kw_batch* b, const kw_env* env, const int32_t* policies, uint32_t npol, const uint64_t* rows,
+                   const uint32_t* cols, size_t n, kw_messages* out) {
+  if (!out) return KW_E_ARG;
+  out->bytes = out->nhost = 0;
+  uint64_t nrows = 0;
+  uint32_t rw = 0;
+  if (!env || kw_batch_last_pass(b, &nrows, &rw) != KW_OK) return KW_E_ARG;
+  DeviceBatch& D = *b->dev;
+  if (D.last_rows_mode || (nrows >> 32) || nrows != b->b.n || npol != rw) return KW_E_ARG;
+  if (D.split && D.perm.size() != nrows) return KW_E_ARG;
+  if (!out_ok(out, rows, cols, n)) return KW_E_ARG;
+  for (size_t i = 0; i < n; ++i)
+    if (rows[i] >= nrows || cols[i] >= npol) return KW_E_ARG;
+  std::vector<uint64_t> table;
+  if (int rc = settings_table(env->e, policies, npol, &table)) return rc;
+  D.messages_ran = true;
+  for (uint64_t& v : D.messages_stats) v = 0;
+  if (n == 0) {
+    if (out->off) out->off[0] = 0;
+    return KW_OK;
+  }
+  const bool dbg = Knobs::on<KW_BULK_DEBUG>();
+  const auto t_start = std::chrono::steady_clock::now();
+  const size_t chunk = (size_t)Knobs::num<KW_MESSAGES_CHUNK>(), m_max = std::min(chunk, n);
+  const uint32_t window = msg_window_bytes(Knobs::num<KW_MESSAGES_WINDOW>());
+
+  HIPCHK(hipSetDevice(D.device));
+  hipStream_t s = D.cur ? D.cur : D.stream;
+  if (!D.names) {
+    if (int rc = upload_names(b, s)) return rc;
+    D.messages_stats[4] = 1;
+  }
+  const double names_ms = ms_since(t_start);
+  if (D.split) D.device_rows();
+
+  // in: [device rows][cols][settings]; out: [off][words][marks][head]; the device's lengths and the scan's tile sums beside them
+  const size_t b_idx = up256(m_max * 4), b_set = up256(table.size() * 8), b_in = 2 * b_idx + b_set;
+  const size_t b_off = up256((m_max + 1) * 8), b_words = up256(m_max * 4), b_mark = up256(m_max),
+               b_out = b_off + b_words + b_mark + up256(sizeof(MessagesHead));
+  constexpr size_t kBounce = (size_t)64 << 20;
+  BlockLease din, dout, dlen, dtext, hin, hout, bounce;
+  Drain drain{s};
+  HIPCHK(hin.alloc(host_pool(), D.device, b_in));
+  HIPCHK(hout.alloc(host_pool(), D.device, b_out));
+  HIPCHK(din.alloc(dev_pool(), D.device, b_in));
+  HIPCHK(dout.alloc(dev_pool(), D.device, b_out));
+  HIPCHK(dlen.alloc(dev_pool(), D.device, b_idx + up256((m_max / kMsgScanTile + 1) * 8)));
+  uint8_t *hi = (uint8_t*)hin.p, *ho = (uint8_t*)hout.p, *di = (uint8_t*)din.p, *dov = (uint8_t*)dout.p;
+  memcpy(hi + 2 * b_idx, table.data(), table.size() * 8);
+  HIPCHK(hipMemcpyAsync(di + 2 * b_idx, hi + 2 * b_idx, b_set, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(dov + b_off + b_words + b_mark, 0, sizeof(MessagesHead), s));
+
+  MessagesArgs a{};
+  a.words = D.verdicts;
+  a.cols.c = device_cols(b);
+  a.cols.name = DigestStr{D.name_col.off, D.name_col.bytes, D.name_col.n};
+  a.settings = di + 2 * b_idx;
+  a.drow = (const uint32_t*)di;
+  a.col = (const uint32_t*)(di + b_idx);
+  a.len = (uint32_t*)dlen.p;
+  a.sums = (uint64_t*)((uint8_t*)dlen.p + b_idx);
+  a.out_words = out->words ? (uint32_t*)(dov + b_off) : nullptr;
+  a.mark = dov + b_off + b_words;
+  a.off = (uint64_t*)dov;
+  a.head = (MessagesHead*)(dov + b_off + b_words + b_mark);
+  a.npol = npol;
+  a.window = window;
+
+  const bool direct = out->cap && page_locked(out->text);
+  StreamTimer t_len(dbg), t_scan(dbg), t_write(dbg), t_back(dbg);
+  double len_ms = 0, scan_ms = 0, write_ms = 0, back_ms = 0, text_ms = 0;
+  uint64_t total = 0, nhost = 0, rounds = 0;
+  for (size_t r0 = 0; r0 < n; r0 += chunk, ++rounds) {
+    const size_t m = std::min(chunk, n - r0);
+    uint32_t *hr = (uint32_t*)hi, *hc = (uint32_t*)(hi + b_idx);
+    HostWorkers::get().run((m + kTask - 1) / kTask, [&](size_t q) {
+      for (size_t i = q * kTask, e = std::min(m, (q + 1) * kTask); i < e; ++i) {
+        hr[i] = (uint32_t)(D.split ? D.inv_perm[rows[r0 + i]] : rows[r0 + i]);
+        hc[i] = cols[r0 + i];
+      }
+    });
+    HIPCHK(hipMemcpyAsync(di, hi, m * 4, hipMemcpyHostToDevice, s));  // (the round's items, not the block)
+    HIPCHK(hipMemcpyAsync(di + b_idx, hi + b_idx, m * 4, hipMemcpyHostToDevice, s));
+    a.n = (uint32_t)m;
+    a.base = total;
+    t_len.start(s);
+    HIPCHK(launch_messages_len(a, s));
+    t_len.stop(s);
+    t_scan.start(s);
+    HIPCHK(launch_messages_scan(a, s));
+    t_scan.stop(s);
+    t_back.start(s);
+    // what the round wrote, sized by its items: the offsets, the words when asked for, the marks, the head
+    HIPCHK(hipMemcpyAsync(ho, dov, (m + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (out->words) HIPCHK(hipMemcpyAsync(ho + b_off, dov + b_off, m * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ho + b_off + b_words, dov + b_off + b_words, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ho + b_off + b_words + b_mark, dov + b_off + b_words + b_mark, sizeof(MessagesHead), hipMemcpyDeviceToHost, s));
+    t_back.stop(s);
+    HIPCHK(hipStreamSynchronize(s));
+    len_ms += t_len.ms(), scan_ms += t_scan.ms(), back_ms += t_back.ms();
+    const MessagesHead head = *(const MessagesHead*)(ho + b_off + b_words + b_mark);
+    if (head.missing) return KW_E_ARG;  // a message quotes a string column that is not resident
+    const uint64_t* off = (const uint64_t*)ho;
+    if (off[0] != total) return KW_E_ENGINE;
+    parallel_copy(out->off + r0, off, (m + 1) * 8);
+    if (out->words) parallel_copy(out->words + r0, ho + b_off, m * 4);
+    const uint8_t* mark = ho + b_off + b_words;  // (marks are rare: eight at a time)
+    for (size_t i = 0; i < m;) {
+      uint64_t eight = 0;
+      if (i + 8 <= m) {
+        memcpy(&eight, mark + i, 8);
+        if (!eight) {
+          i += 8;
+          continue;
+        }
+      }
+      for (const size_t e = std::min(m, i + 8); i < e; ++i)
+        if (mark[i]) {
+          if (nhost < out->host_cap) out->host[nhost] = r0 + i;
+          ++nhost;
+        }
+    }
+    const uint64_t end = off[m];
+    if (end > total && end <= out->cap) {  // (past cap only the lengths run: text is then unspecified)
+      a.text_base = total & ~(uint64_t)15u;
+      const size_t b_text = (size_t)(end - a.text_base) + 16;
+      HIPCHK(dtext.alloc(dev_pool(), D.device, b_text));
+      a.text = (uint8_t*)dtext.p;
+      t_write.start(s);
+      HIPCHK(launch_messages_write(a, s));
+      t_write.stop(s);
+      const uint8_t* src = a.text + (total - a.text_base);
+      const size_t bytes = (size_t)(end - total);
+      const auto t_text = std::chrono::steady_clock::now();
+      if (direct) {
+        HIPCHK(hipMemcpyAsync(out->text + total, src, bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+      } else {
+        if (!bounce.p) HIPCHK(bounce.alloc(host_pool(), D.device, std::min(kBounce, std::max<size_t>(bytes, 4096))));
+        const size_t per = bounce.bytes;
+        for (size_t at = 0; at < bytes; at += per) {
+          const size_t k = std::min(per, bytes - at);
+          HIPCHK(hipMemcpyAsync(bounce.p, src + at, k, hipMemcpyDeviceToHost, s));
+          HIPCHK(hipStreamSynchronize(s));
+          parallel_copy(out->text + total + at, bounce.p, k);
+        }
+      }
+      write_ms += t_write.ms();
+      text_ms += ms_since(t_text);
+    }
+    total = end;
+  }
+  out->bytes = (size_t)total;
+  out->nhost = (size_t)nhost;
+  // the counters of the write launches
+  HIPCHK(hipMemcpyAsync(ho, a.head, sizeof(MessagesHead), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const MessagesHead head = *(const MessagesHead*)ho;
+  D.messages_stats[0] = rounds;
+  D.messages_stats[1] = head.windows;
+  D.messages_stats[2] = head.spanning;
+  D.messages_stats[3] = nhost;
+  const bool fits = total <= out->cap && nhost <= out->host_cap;
+  if (dbg)
+    fprintf(stderr, "[kw messages] %zu items, %llu bytes, %llu for the host, %llu rounds, window %u%s: names %.3f ms, len %.3f ms scan %.3f ms "
+            "write %.3f ms on the device (by events), offsets read-back %.3f ms (by events), text read-back %.3f ms (%s), the call %.3f ms\n",
+            n, (unsigned long long)total, (unsigned long long)nhost, (unsigned long long)rounds, window, fits ? "" : " (more than cap)",
+            names_ms, len_ms, scan_ms, write_ms, back_ms, text_ms, direct ? "direct" : "bounce", ms_since(t_start));
+  return fits ? KW_OK : KW_E_NOSPACE;
+}
+
+// The host side over full words [nrows][npol] and the host batch. how 0: policy_message per item;
+// how 1: the piece renderer over the host columns.
+int debug_messages_words(const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol, const uint32_t* words,
+                         uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int how, kw_messages* out) {
+  if (!out) return KW_E_ARG;
+  out->bytes = out->nhost = 0;
+  if (!env || !b || npol == 0 || nrows > b->b.n || (nrows && !words) || (how != 0 && how != 1)) return KW_E_ARG;
+  if (!out_ok(out, rows, cols, n)) return KW_E_ARG;
+  for (size_t i = 0; i < n; ++i)
+    if (rows[i] >= nrows || cols[i] >= npol) return KW_E_ARG;
+  std::vector<uint64_t> table;
+  if (int rc = settings_table(env->e, policies, npol, &table)) return rc;
+  if (n == 0) {
+    if (out->off) out->off[0] = 0;
+    return KW_OK;
+  }
+  const MsgCols C = host_msg_cols(b->b);
+  const MsgSettings S = msg_settings((const uint8_t*)table.data());
+  uint64_t total = 0, nhost = 0;
+  std::string msg;
+  MsgPlan P;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t w = words[rows[i] * npol + cols[i]];
+    out->off[i] = total;
+    if (out->words) out->words[i] = w;
+    bool host = false;
+    size_t len = 0;
+    if (how == 0) {
+      msg.clear();
+      host = msg_word_host(w);
+      if (!host) {
+        const Status st = policy_message(env->e, b->b, rows[i], policies[cols[i]], KW_REASON(w), KW_ARG(w), &msg);
+        if (!st.ok()) {
+          host = true;
+          msg.clear();
+        }
+      }
+      len = msg.size();
+      if (len && total + len <= out->cap) memcpy(out->text + total, msg.data(), len);
+    } else {
+      const uint32_t st = message_pieces(C, S, rows[i], cols[i], w, &P);
+      if (st == MSG_MISSING) return KW_E_ARG;
+      host = st == MSG_HOST;
+      len = P.len;
+      if (len && total + len <= out->cap) msg_copy_window(P, 0, P.len, (uint8_t*)out->text + total);
+    }
+    if (host) {
+      if (nhost < out->host_cap) out->host[nhost] = i;
+      ++nhost;
+    }
+    total += len;
+  }
+  out->off[n] = total;
+  out->bytes = (size_t)total;
+  out->nhost = (size_t)nhost;
+  return total <= out->cap && nhost <= out->host_cap ? KW_OK : KW_E_NOSPACE;
+}
+
+int debug_messages_stats(const kw_batch* b, uint64_t* out) {
+  if (!b || !b->dev || !out || !b->dev->messages_ran) return KW_E_ARG;
+  for (int i = 0; i < 5; ++i) out[i] = b->dev->messages_stats[i];
+  return KW_OK;
+}
+
+}  // namespace kw

@@ -121,4 +121,12 @@ int load_side_data(kw_batch* b, hipStream_t s);
 // side data.
 int read_verdicts(kw_batch* b, uint32_t* host_out, size_t count);
 
+// The messages of chosen findings (messages.cpp): kw_batch_messages over the last all-pairs pass,
+// and the host renderers and the statistics of the diagnostics.
+int batch_messages(kw_batch* b, const kw_env* env, const int32_t* policies, uint32_t npol, const uint64_t* rows,
+                   const uint32_t* cols, size_t n, kw_messages* out);
+int debug_messages_words(const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol, const uint32_t* words,
+                         uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int how, kw_messages* out);
+int debug_messages_stats(const kw_batch* b, uint64_t* out);
+
 }  // namespace kw

@@ -487,6 +487,25 @@ class MembersNoSpace(NoSpace):
 Members = collections.namedtuple("Members", ["off", "rows", "words"])
 
 
+class MessagesNoSpace(NoSpace):
+    """KW_E_NOSPACE of a messages call: .need text bytes and .nhost host items are required; .off holds
+    the exact bounds."""
+
+    def __init__(self, need, off, nhost):
+        Exception.__init__(self, f"the messages need {need} bytes and {nhost} host items")
+        self.need, self.off, self.nhost = int(need), off, int(nhost)
+
+
+class Messages(collections.namedtuple("Messages", ["off", "text", "words", "host"])):
+    """off uint64 [n + 1], text uint8 [off[n]], words uint32 [n] or None, host uint64 (the items left
+    to format_response, ascending)."""
+    __slots__ = ()
+
+    def get(self, i):
+        """Message i as bytes (raw UTF-8, b"" for an item left to the host)."""
+        return self.text[int(self.off[i]):int(self.off[i + 1])].tobytes()
+
+
 class Batch:
     """A micro-batch of requests in SoA form (kw_batch)."""
 
@@ -813,6 +832,84 @@ class Batch:
         wp = words.ctypes.data_as(C.POINTER(C.c_uint32))
         return self._members_call(lambda p, n, st: self._L.kw_debug_digest_members_words(self._h, wp, nrows, npol, p, n, st),
                                   recs, with_words, cap)
+
+    @staticmethod
+    def _messages_call(call, rows, cols, words, cap, host_cap=None):
+        """call(rows pointer, cols pointer, n, struct) into a text buffer of `cap` bytes: without `cap`
+        sized from a first KW_E_NOSPACE answer and grown once; a `cap` (or `host_cap`) that is given and
+        too small raises MessagesNoSpace."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1)
+        if rows.size != cols.size:
+            raise ValueError("rows and cols must pair up")
+        n = rows.size
+        grow = cap is None and host_cap is None
+        cap = 0 if cap is None else cap
+        host_cap = n if host_cap is None else host_cap
+        off = np.zeros(n + 1, dtype=np.uint64)
+        wd = np.zeros(max(n, 1), dtype=np.uint32) if words else None
+        for attempt in (0, 1):
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            host = np.zeros(max(host_cap, 1), dtype=np.uint64)
+            st = N.KwMessages(off.ctypes.data_as(C.POINTER(C.c_uint64)), text.ctypes.data, cap, 0,
+                              wd.ctypes.data_as(C.POINTER(C.c_uint32)) if words else None,
+                              host.ctypes.data_as(C.POINTER(C.c_uint64)), host_cap, 0)
+            rc = call(rows.ctypes.data_as(C.POINTER(C.c_uint64)), cols.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(st))
+            if rc != N.KW_E_NOSPACE:
+                break
+            if not grow or attempt:
+                raise MessagesNoSpace(st.bytes, off, st.nhost)
+            cap = st.bytes
+        raise_for(rc, "the messages failed")
+        return Messages(off, text[:st.bytes], wd[:n] if words else None, host[:st.nhost])
+
+    def messages(self, env, policies, rows, cols, words=False, cap=None, host_cap=None):
+        """The messages of the items (rows[i], cols[i]) of the last all-pairs device pass over
+        `policies` (kw_batch_messages), rendered on the device: Messages(off, text, words, host), item
+        i's message text[off[i]:off[i + 1]] (Messages.get(i)), raw UTF-8; the items in `host` have the
+        empty message here and are left to format_response. Without `cap` the text is sized from a
+        first KW_E_NOSPACE answer and grown once: that is two calls of the library, the first of
+        which runs every length round and its read-back (only the write and the text's copy are
+        skipped), so it costs well over half of a second call; a caller that knows a bound passes
+        `cap` and pays for one. With `cap` a call that needs more raises MessagesNoSpace (.need, .off,
+        .nhost)."""
+        arr = env._array(policies)
+        return self._messages_call(lambda r, c, n, st: self._L.kw_batch_messages(self._h, env._h, arr, len(policies), r, c, n, st),
+                                   rows, cols, words, cap, host_cap)
+
+    def messages_from_words(self, env, policies, words, rows, cols, how=0, with_words=False, cap=None, host_cap=None):
+        """Diagnostic (kw_debug_messages_words): the same output on the host from full words
+        [rows][npol] and this batch's host columns. how=0: one policy_message per item (the reference);
+        how=1: the piece renderer the device runs."""
+        import numpy as np
+        arr = env._array(policies)
+        npol = len(policies)
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        nrows = words.size // npol
+        wp = words.ctypes.data_as(C.POINTER(C.c_uint32))
+        return self._messages_call(
+            lambda r, c, n, st: self._L.kw_debug_messages_words(env._h, self._h, arr, npol, wp, nrows, r, c, n, how, st),
+            rows, cols, with_words, cap, host_cap)
+
+    def member_messages(self, env, policies, recs, members, words=False, cap=None):
+        """The messages of the members of digest groups: `members` is digest_members(recs); group g's
+        members are the pairs (members.rows[off[g]:off[g + 1]], recs[g].col). One messages() call over
+        them all, in the members' order. The members say how many messages there are, not how long
+        they are: without `cap` this is messages()'s two calls of the library, with it one."""
+        import numpy as np
+        recs = np.ascontiguousarray(recs, dtype=np.dtype(DIGEST_REC)).reshape(-1)
+        counts = np.diff(members.off.astype(np.int64))
+        cols = np.repeat(recs["col"].astype(np.uint32), counts)
+        return self.messages(env, policies, members.rows, cols, words=words, cap=cap)
+
+    def debug_messages_stats(self):
+        """Diagnostic (kw_debug_messages_stats): what the last messages() did, as a dict: the rounds,
+        the staging windows written, the messages that spanned a window, the items left to the host,
+        whether the call uploaded the container names."""
+        out = (C.c_uint64 * 5)()
+        raise_for(self._L.kw_debug_messages_stats(self._h, out), "the batch never rendered messages")
+        return dict(zip(("rounds", "windows", "spanning", "host", "uploaded_names"), (int(x) for x in out)))
 
     def finding_key(self, row, word):
         """The key bytes of the finding `word` at batch row `row` (kw_batch_finding_key), host only:
