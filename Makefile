@@ -16,7 +16,7 @@ HIPDEF := -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra $(HIPDEF)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -munsafe-fp-atomics $(HIPEXTRA)
 
-HOST_SRCS := json yaml automaton expr env flatten service slotplan metrics knobs pools plan pass upload bulk bulkout packed summary outcomes digest members messages capi
+HOST_SRCS := json yaml automaton expr env flatten service slotplan metrics knobs pools plan pass upload bulk bulkout packed lastpass summary outcomes digest members messages capi
 HOST_OBJS := $(addprefix $(OBJ)/,$(addsuffix .o,$(HOST_SRCS)))
 HEADERS := $(wildcard $(SRC)/*.hpp) include/kwgpu.h
 
@@ -38,11 +38,12 @@ $(OBJ)/%.o: $(SRC)/%.cpp $(HEADERS)
 	@mkdir -p $(OBJ)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-$(OBJ)/kernels.o: $(SRC)/kernels.hip $(HEADERS)
+# the device objects: the hot path (kernels.hip) and the reports over its verdict words (reports.hip)
+$(OBJ)/kernels.o $(OBJ)/reports.o: $(OBJ)/%.o: $(SRC)/%.hip $(HEADERS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(PKG)/libkwgpu.so: $(HOST_OBJS) $(OBJ)/kernels.o
+$(PKG)/libkwgpu.so: $(HOST_OBJS) $(OBJ)/kernels.o $(OBJ)/reports.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 $(PKG)/kwhost: $(SRC)/kwhost.cpp include/kwgpu.h $(PKG)/libkwgpu.so
@@ -60,11 +61,12 @@ oracle/build/libkworacle.so: oracle/kworacle.c oracle/kwregex.c oracle/kworacle.
 
 # A/B variant of the library with extra kernel flags: make variant NAME=x VFLAGS="-DKW_PREFETCH=0"
 # -> policy-server_amd/variants/x.so (KWGPU_LIB selects it; scripts/ab.sh benches every variant);
-# KSRC=<file in csrc/> builds another kernels source (e.g. the previous commit's)
+# KSRC=<file in csrc/> builds another kernels source in place of kernels.hip (e.g. the previous commit's)
 variant: $(HOST_OBJS)
 	@mkdir -p $(PKG)/variants/obj-$(NAME)
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(or $(KSRC),$(SRC)/kernels.hip) -o $(PKG)/variants/obj-$(NAME)/kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(HOST_OBJS) $(PKG)/variants/obj-$(NAME)/kernels.o
+	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(SRC)/reports.hip -o $(PKG)/variants/obj-$(NAME)/reports.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(HOST_OBJS) $(PKG)/variants/obj-$(NAME)/kernels.o $(PKG)/variants/obj-$(NAME)/reports.o
 
 # A/B variant built entirely (host engine + kernels) from another source directory next to csrc/,
 # e.g. a snapshot of an earlier commit: make variant-full NAME=x VSRC=policy-server_amd/csrc_x
@@ -72,11 +74,12 @@ variant-full:
 	@mkdir -p $(PKG)/variants/obj-$(NAME)
 	for f in $(HOST_SRCS); do $(CXX) $(CXXFLAGS) $(VFLAGS) -c $(VSRC)/$$f.cpp -o $(PKG)/variants/obj-$(NAME)/$$f.o || exit 1; done
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(VSRC)/kernels.hip -o $(PKG)/variants/obj-$(NAME)/kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(addprefix $(PKG)/variants/obj-$(NAME)/,$(addsuffix .o,$(HOST_SRCS))) $(PKG)/variants/obj-$(NAME)/kernels.o
+	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(VSRC)/reports.hip -o $(PKG)/variants/obj-$(NAME)/reports.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(addprefix $(PKG)/variants/obj-$(NAME)/,$(addsuffix .o,$(HOST_SRCS))) $(PKG)/variants/obj-$(NAME)/kernels.o $(PKG)/variants/obj-$(NAME)/reports.o
 
 # kernel resource usage (VGPR/SGPR/LDS/occupancy) report
-resources: $(SRC)/kernels.hip
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o /dev/null
+resources: $(SRC)/kernels.hip $(SRC)/reports.hip
+	for f in $^; do $(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $$f -o /dev/null || exit 1; done
 
 clean:
 	rm -rf $(OBJ) $(PKG)/*.so $(PKG)/kwhost $(PKG)/kwload oracle/build

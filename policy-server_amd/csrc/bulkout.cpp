@@ -5,7 +5,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "kernels.hpp"
+#include "reports.hpp"
 #include "knobs.hpp"
 #include "packed.hpp"
 

@@ -12,6 +12,7 @@
 
 #include "../../include/kwgpu.h"
 #include "batch.hpp"
+#include "digest.hpp"
 #include "env.hpp"
 #include "kernels.hpp"
 #include "pools.hpp"

@@ -2,7 +2,7 @@
 // last pass's findings into a table on the device by (column, reason, allowed bit, key), verifies
 // every finding against its group's representative, reads back the records, folds the few findings
 // the verify launch hands over into them by the exact reducer and sorts; the host-reducer
-// diagnostic; the key of one finding. The arithmetic is digest.hpp's, the kernels kernels.hip's.
+// diagnostic; the key of one finding. The arithmetic is digest.hpp's, the kernels reports.hip's.
 #include "digest.hpp"
 
 #include <chrono>
@@ -10,10 +10,9 @@
 #include <cstring>
 #include <vector>
 
-#include "devbatch.hpp"
-#include "kernels.hpp"
 #include "knobs.hpp"
-#include "pass.hpp"
+#include "lastpass.hpp"
+#include "reports.hpp"
 
 namespace kw {
 namespace {
@@ -23,13 +22,6 @@ static_assert(same_col(DG_NS, S_NS) && same_col(DG_IMG, S_IMG) && same_col(DG_AA
                   same_col(DG_LK, S_LK) && same_col(DG_LV, S_LV) && same_col(DG_NSTR, NSTR),
               "digest.hpp numbers the string columns as kernels.hpp Str");
 static_assert(sizeof(DigestSlot) == 24 && sizeof(DigestLeft) == 16 && sizeof(kw_digest_rec) == 24, "digest records");
-
-// Declared after the leases a call holds: the stream is drained before any block returns to its pool,
-// on the error returns too.
-struct Drain {
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
 
 }  // namespace
 
@@ -68,21 +60,16 @@ DigestCols device_cols(const kw_batch* kb) {
 
 namespace {
 
-double ms_since(std::chrono::steady_clock::time_point t) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
 int batch_digest(kw_batch* b, kw_digest* out) {
   if (!out) return KW_E_ARG;
   out->n = out->nwide = 0;
   out->findings = 0;
-  uint64_t rows = 0;
-  uint32_t npol = 0;
-  if (kw_batch_last_pass(b, &rows, &npol) != KW_OK) return KW_E_ARG;
-  DeviceBatch& D = *b->dev;
-  if (D.last_rows_mode || (rows >> 32) || rows != b->b.n) return KW_E_ARG;
+  LastPass F(b, LastPass::kWholeBatch);
+  if (!F.ok()) return KW_E_ARG;
   if ((out->cap && !out->recs) || (out->wide_cap && !out->wide)) return KW_E_ARG;
-  if (D.split && D.perm.size() != rows) return KW_E_ARG;
+  const uint64_t rows = F.rows;
+  const uint32_t npol = F.npol;
+  DeviceBatch& D = *F.dev;
   D.digest_ran = true;
   for (uint64_t& v : D.digest_stats) v = 0;
   if (rows == 0) return KW_OK;
@@ -92,10 +79,10 @@ int batch_digest(kw_batch* b, kw_digest* out) {
   const uint32_t hash_bits = (uint32_t)Knobs::num<KW_DIGEST_HASH_BITS>();
   const uint64_t max_slots = digest_slots(budget, rows * npol), wide_cap = rows;
 
-  HIPCHK(hipSetDevice(D.device));
-  hipStream_t s = D.cur ? D.cur : D.stream;
-  BlockLease dtable, dhead, dwide, dleft, drecs, dmap, hhead, hmap, hback;
-  Drain drain{s};
+  if (int rc = F.open()) return rc;
+  hipStream_t s = F.s;
+  BlockLease &dtable = F.lease(), &dhead = F.lease(), &dwide = F.lease(), &dleft = F.lease(), &drecs = F.lease(),
+             &hhead = F.lease(), &hback = F.lease();
   HIPCHK(dtable.alloc(dev_pool(), D.device, (size_t)max_slots * sizeof(DigestSlot)));
   HIPCHK(dhead.alloc(dev_pool(), D.device, sizeof(DigestHead)));
   HIPCHK(dwide.alloc(dev_pool(), D.device, (size_t)wide_cap * 8));
@@ -114,19 +101,8 @@ int batch_digest(kw_batch* b, kw_digest* out) {
   a.hash_bits = hash_bits;
   a.npol = npol;
   a.loaded = D.loaded;
-  if (D.split) {  // the verdict buffer is in device-row order, first_row speaks batch rows
-    const std::vector<uint64_t>& dev_row = D.device_rows();
-    HIPCHK(hmap.alloc(host_pool(), D.device, (size_t)rows * 8));
-    HIPCHK(dmap.alloc(dev_pool(), D.device, (size_t)rows * 8));
-    uint32_t* m = (uint32_t*)hmap.p;
-    for (uint64_t i = 0; i < rows; ++i) {
-      m[i] = (uint32_t)D.perm[i];
-      m[rows + i] = (uint32_t)dev_row[i];
-    }
-    HIPCHK(hipMemcpyAsync(dmap.p, hmap.p, (size_t)rows * 8, hipMemcpyHostToDevice, s));
-    a.d2b = (const uint32_t*)dmap.p;
-    a.b2d = a.d2b + rows;
-  }
+  // (a split batch: the verdict buffer is in device-row order, first_row speaks batch rows)
+  if (int rc = upload_row_maps(F, &a.d2b, &a.b2d)) return rc;
   const double prep_ms = ms_since(t_start);
 
   const DigestCols H = host_cols(b->b);

@@ -2,7 +2,7 @@
 // finding's key is (the bytes its message quotes from the request, or its argument as a number), the
 // hash and the equality of (column, reason, allowed bit, key), the exact host reducer over words
 // [rows][npol], the order and the capacity check of the output, and the geometry of the device
-// reduction (kernels.hip digest_*_kernel): the hash table's size under a byte budget, the status of
+// reduction (reports.hip digest_*_kernel): the hash table's size under a byte budget, the status of
 // one column range and the cut of the columns into halves. No HIP, no batch, no settings
 // (tests/digest_check.cpp runs it on the host).
 //

@@ -2,7 +2,7 @@
 // kw_batch_digest_members builds the selection table of the named groups on the host, checks every
 // record's word against the pass and walks the words once on the device, reads back the per-group
 // counts and the members found, and orders them by (group, row) on the host workers; the
-// host-reducer diagnostic. The arithmetic is members.hpp's, the kernels kernels.hip's.
+// host-reducer diagnostic. The arithmetic is members.hpp's, the kernels reports.hip's.
 #include "members.hpp"
 
 #include <chrono>
@@ -11,38 +11,23 @@
 #include <functional>
 #include <vector>
 
-#include "devbatch.hpp"
-#include "kernels.hpp"
 #include "knobs.hpp"
-#include "pass.hpp"
+#include "lastpass.hpp"
+#include "reports.hpp"
 
 namespace kw {
 namespace {
 
 static_assert(sizeof(MemberSlot) == 32 && sizeof(MemberEntry) == 16 && sizeof(MembersHead) == 16, "members records");
 
-// Declared after the leases a call holds: the stream is drained before any block returns to its pool,
-// on the error returns too.
-struct Drain {
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
-size_t up16(size_t n) { return (n + 15u) & ~(size_t)15u; }
-
 int batch_members(kw_batch* b, const kw_digest_rec* groups, size_t ngroups, kw_members* out) {
   if (!out) return KW_E_ARG;
   out->n = 0;
-  uint64_t rows = 0;
-  uint32_t npol = 0;
-  if (kw_batch_last_pass(b, &rows, &npol) != KW_OK) return KW_E_ARG;
-  DeviceBatch& D = *b->dev;
-  if (D.last_rows_mode || (rows >> 32) || rows != b->b.n) return KW_E_ARG;
-  if (D.split && D.perm.size() != rows) return KW_E_ARG;
+  LastPass F(b, LastPass::kWholeBatch);
+  if (!F.ok()) return KW_E_ARG;
+  const uint64_t rows = F.rows;
+  const uint32_t npol = F.npol;
+  DeviceBatch& D = *F.dev;
   if (!members_out_ok(groups, ngroups, out)) return KW_E_ARG;
   if (ngroups == 0) {
     if (out->off) out->off[0] = 0;
@@ -57,20 +42,16 @@ int batch_members(kw_batch* b, const kw_digest_rec* groups, size_t ngroups, kw_m
   const DigestCols H = host_cols(b->b);
   if (int rc = members_table(H, groups, ngroups, rows, npol, hash_bits, D.split ? D.device_rows().data() : nullptr, &T)) return rc;
   const DigestCols C = device_cols(b);
-  uint32_t have = 0;
-  for (uint32_t m = 0; m < DG_NSTR; ++m)
-    if (C.str[m].off) have |= 1u << m;
+  const uint32_t have = resident_mask(C);
   if (members_need(groups, ngroups) & ~have) return KW_E_ARG;  // a key column that is not resident
   const uint64_t pairs = rows * npol, list_cap = std::min<uint64_t>(out->cap, pairs);
   const double table_ms = ms_since(t_start);
 
-  HIPCHK(hipSetDevice(D.device));
-  hipStream_t s = D.cur ? D.cur : D.stream;
-  BlockLease din, dacc, dlist, hin, hacc, hlist;
-  Drain drain{s};
-  // in: [slots][column masks][row map]; acc: [head][counts]
-  const size_t b_slots = T.slots.size() * sizeof(MemberSlot), b_mask = up16((size_t)npol * 8),
-               b_map = D.split ? up16((size_t)rows * 4) : 0, b_in = b_slots + b_mask + b_map;
+  if (int rc = F.open()) return rc;
+  hipStream_t s = F.s;
+  BlockLease &din = F.lease(), &dacc = F.lease(), &dlist = F.lease(), &hin = F.lease(), &hacc = F.lease(), &hlist = F.lease();
+  // in: [slots][column masks]; acc: [head][counts]
+  const size_t b_slots = T.slots.size() * sizeof(MemberSlot), b_in = b_slots + (size_t)npol * 8;
   const size_t b_acc = sizeof(MembersHead) + ngroups * 8;
   HIPCHK(hin.alloc(host_pool(), D.device, b_in));
   HIPCHK(din.alloc(dev_pool(), D.device, b_in));
@@ -80,10 +61,6 @@ int batch_members(kw_batch* b, const kw_digest_rec* groups, size_t ngroups, kw_m
   uint8_t* hi = (uint8_t*)hin.p;
   memcpy(hi, T.slots.data(), b_slots);
   memcpy(hi + b_slots, T.colmask.data(), (size_t)npol * 8);
-  if (D.split) {  // the verdict buffer is in device-row order, the members speak batch rows
-    uint32_t* m = (uint32_t*)(hi + b_slots + b_mask);
-    for (uint64_t i = 0; i < rows; ++i) m[i] = (uint32_t)D.perm[i];
-  }
   HIPCHK(hipMemcpyAsync(din.p, hin.p, b_in, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(dacc.p, 0, b_acc, s));
 
@@ -92,7 +69,8 @@ int batch_members(kw_batch* b, const kw_digest_rec* groups, size_t ngroups, kw_m
   a.cols = C;
   a.table = (const MemberSlot*)din.p;
   a.colmask = (const uint64_t*)((const uint8_t*)din.p + b_slots);
-  a.d2b = D.split ? (const uint32_t*)((const uint8_t*)din.p + b_slots + b_mask) : nullptr;
+  // (a split batch: the verdict buffer is in device-row order, the members speak batch rows)
+  if (int rc = upload_row_maps(F, &a.d2b)) return rc;
   a.head = (MembersHead*)dacc.p;
   a.counts = (uint64_t*)((uint8_t*)dacc.p + sizeof(MembersHead));
   a.list = (MemberEntry*)dlist.p;

@@ -2,7 +2,7 @@
 // kw_batch_digest_members): which findings of a pass are the members of the groups a caller names by
 // their digest records. The validation of a record list, the exact host reducer over words
 // [rows][npol] (an ordered map over DigestId, no hashing), the selection table the device walk probes
-// (kernels.hip members_*_kernel) with its geometry and its per-column class masks, the probe itself
+// (reports.hip members_*_kernel) with its geometry and its per-column class masks, the probe itself
 // (host and device run the same function), and the order and the capacity check of the output. The
 // key, the hash, the tag and the class are digest.hpp's, unchanged. No HIP, no batch, no settings
 // (tests/members_check.cpp runs it on the host).

@@ -4,7 +4,7 @@
 // steps a round, the offsets, the words and the host marks come back through a pooled block, the
 // text by direct DMA into page-locked memory or through a bounce block. The steps of a round run
 // serially on the pass's stream (the next round's base is the total the host reads back). The two
-// host renderers of the diagnostic. The arithmetic is messages.hpp's, the kernels kernels.hip's.
+// host renderers of the diagnostic. The arithmetic is messages.hpp's, the kernels reports.hip's.
 #include "messages.hpp"
 
 #include <chrono>
@@ -13,10 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "devbatch.hpp"
-#include "kernels.hpp"
 #include "knobs.hpp"
-#include "pass.hpp"
+#include "lastpass.hpp"
+#include "reports.hpp"
 #include "service.hpp"
 #include "upload.hpp"
 
@@ -25,18 +24,6 @@ namespace {
 
 static_assert(sizeof(MsgCol) == 44 && sizeof(MsgCons) == 16 && sizeof(MsgHead) == 16 && sizeof(MessagesHead) == 24, "messages records");
 
-// Declared after the leases a call holds: the stream is drained before any block returns to its pool,
-// on the error returns too.
-struct Drain {
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
-size_t up256(size_t n) { return (n + 255u) & ~(size_t)255u; }
 constexpr size_t kTask = 1u << 16;  // items of one staging task of the host workers
 
 // The settings table of a pass over `policies` (msg_build_table); KW_E_ARG for an index outside the
@@ -82,7 +69,7 @@ int upload_names(kw_batch* kb, hipStream_t s) {
   const StrCol& N = B.ctr_name;
   const uint64_t nc = B.containers();
   if (N.n() != nc) return KW_E_ARG;
-  const size_t b_off = up256((size_t)(nc + 1) * 4), b_bytes = up256((size_t)N.off.back() + 32), total = b_off + b_bytes;
+  const size_t b_off = round_up((size_t)(nc + 1) * 4, 256), b_bytes = round_up((size_t)N.off.back() + 32, 256), total = b_off + b_bytes;
   BlockLease h;
   HIPCHK(h.alloc(host_pool(), D.device, total));
   uint32_t* off = (uint32_t*)h.p;
@@ -127,12 +114,10 @@ int batch_messages(kw_batch* b, const kw_env* env, const int32_t* policies, uint
                    const uint32_t* cols, size_t n, kw_messages* out) {
   if (!out) return KW_E_ARG;
   out->bytes = out->nhost = 0;
-  uint64_t nrows = 0;
-  uint32_t rw = 0;
-  if (!env || kw_batch_last_pass(b, &nrows, &rw) != KW_OK) return KW_E_ARG;
-  DeviceBatch& D = *b->dev;
-  if (D.last_rows_mode || (nrows >> 32) || nrows != b->b.n || npol != rw) return KW_E_ARG;
-  if (D.split && D.perm.size() != nrows) return KW_E_ARG;
+  LastPass F(b, LastPass::kWholeBatch);
+  if (!env || !F.ok() || npol != F.npol) return KW_E_ARG;
+  const uint64_t nrows = F.rows;
+  DeviceBatch& D = *F.dev;
   if (!out_ok(out, rows, cols, n)) return KW_E_ARG;
   for (size_t i = 0; i < n; ++i)
     if (rows[i] >= nrows || cols[i] >= npol) return KW_E_ARG;
@@ -149,8 +134,8 @@ int batch_messages(kw_batch* b, const kw_env* env, const int32_t* policies, uint
   const size_t chunk = (size_t)Knobs::num<KW_MESSAGES_CHUNK>(), m_max = std::min(chunk, n);
   const uint32_t window = msg_window_bytes(Knobs::num<KW_MESSAGES_WINDOW>());
 
-  HIPCHK(hipSetDevice(D.device));
-  hipStream_t s = D.cur ? D.cur : D.stream;
+  if (int rc = F.open()) return rc;
+  hipStream_t s = F.s;
   if (!D.names) {
     if (int rc = upload_names(b, s)) return rc;
     D.messages_stats[4] = 1;
@@ -159,17 +144,16 @@ int batch_messages(kw_batch* b, const kw_env* env, const int32_t* policies, uint
   if (D.split) D.device_rows();
 
   // in: [device rows][cols][settings]; out: [off][words][marks][head]; the device's lengths and the scan's tile sums beside them
-  const size_t b_idx = up256(m_max * 4), b_set = up256(table.size() * 8), b_in = 2 * b_idx + b_set;
-  const size_t b_off = up256((m_max + 1) * 8), b_words = up256(m_max * 4), b_mark = up256(m_max),
-               b_out = b_off + b_words + b_mark + up256(sizeof(MessagesHead));
-  constexpr size_t kBounce = (size_t)64 << 20;
-  BlockLease din, dout, dlen, dtext, hin, hout, bounce;
-  Drain drain{s};
+  const size_t b_idx = round_up(m_max * 4, 256), b_set = round_up(table.size() * 8, 256), b_in = 2 * b_idx + b_set;
+  const size_t b_off = round_up((m_max + 1) * 8, 256), b_words = round_up(m_max * 4, 256), b_mark = round_up(m_max, 256),
+               b_out = b_off + b_words + b_mark + round_up(sizeof(MessagesHead), 256);
+  BlockLease &din = F.lease(), &dout = F.lease(), &dlen = F.lease(), &dtext = F.lease(), &hin = F.lease(), &hout = F.lease(),
+             &bounce = F.lease();
   HIPCHK(hin.alloc(host_pool(), D.device, b_in));
   HIPCHK(hout.alloc(host_pool(), D.device, b_out));
   HIPCHK(din.alloc(dev_pool(), D.device, b_in));
   HIPCHK(dout.alloc(dev_pool(), D.device, b_out));
-  HIPCHK(dlen.alloc(dev_pool(), D.device, b_idx + up256((m_max / kMsgScanTile + 1) * 8)));
+  HIPCHK(dlen.alloc(dev_pool(), D.device, b_idx + round_up((m_max / kMsgScanTile + 1) * 8, 256)));
   uint8_t *hi = (uint8_t*)hin.p, *ho = (uint8_t*)hout.p, *di = (uint8_t*)din.p, *dov = (uint8_t*)dout.p;
   memcpy(hi + 2 * b_idx, table.data(), table.size() * 8);
   HIPCHK(hipMemcpyAsync(di + 2 * b_idx, hi + 2 * b_idx, b_set, hipMemcpyHostToDevice, s));
@@ -260,15 +244,8 @@ int batch_messages(kw_batch* b, const kw_env* env, const int32_t* policies, uint
       if (direct) {
         HIPCHK(hipMemcpyAsync(out->text + total, src, bytes, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-      } else {
-        if (!bounce.p) HIPCHK(bounce.alloc(host_pool(), D.device, std::min(kBounce, std::max<size_t>(bytes, 4096))));
-        const size_t per = bounce.bytes;
-        for (size_t at = 0; at < bytes; at += per) {
-          const size_t k = std::min(per, bytes - at);
-          HIPCHK(hipMemcpyAsync(bounce.p, src + at, k, hipMemcpyDeviceToHost, s));
-          HIPCHK(hipStreamSynchronize(s));
-          parallel_copy(out->text + total + at, bounce.p, k);
-        }
+      } else if (int rc = bounce_read(bounce, D.device, s, out->text + total, src, bytes)) {
+        return rc;
       }
       write_ms += t_write.ms();
       text_ms += ms_since(t_text);

@@ -5,7 +5,7 @@
 // valid namespace, a mandatory key, a constraint's regex, a group's message, an initialisation
 // error). message_pieces gives the pieces of one item or says "host"; msg_copy_window writes the
 // part of a message that falls into one window of the output, msg_clip and msg_chunks are the
-// window and alignment arithmetic of the write kernel (kernels.hip messages_write_kernel), and
+// window and alignment arithmetic of the write kernel (reports.hip messages_write_kernel), and
 // MsgTable is the settings table as the host builds it. Every function the device runs is KW_HD:
 // the host renderer (kw_debug_messages_words how = 1) runs the same code over the host columns.
 // No HIP, no batch, no settings of the process (tests/messages_check.cpp runs it on the host).

@@ -2,7 +2,7 @@
 // sorts the caller's group ids into a row list, counts the last pass's verdict words on the device
 // per (group, outcome, column) and reads back only the table; kw_batch_attribute_groups builds the
 // dictionary of the rows' metrics attributes on the host workers; the host-reducer diagnostic. The
-// arithmetic is outcomes.hpp's, the kernel kernels.hip's; capi.cpp folds the table into kw_metrics.
+// arithmetic is outcomes.hpp's, the kernel reports.hip's; capi.cpp folds the table into kw_metrics.
 #include "outcomes.hpp"
 
 #include <chrono>
@@ -12,27 +12,20 @@
 #include <unordered_map>
 #include <vector>
 
-#include "devbatch.hpp"
-#include "kernels.hpp"
 #include "knobs.hpp"
-#include "pass.hpp"
+#include "lastpass.hpp"
+#include "reports.hpp"
 
 namespace kw {
 namespace {
 
-// Declared after the leases a call holds: the stream is drained before any block returns to its pool,
-// on the error returns too.
-struct Drain {
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 int batch_outcomes(kw_batch* b, const uint32_t* row_group, uint32_t ngroups, uint64_t* out) {
-  uint64_t rows = 0;
-  uint32_t npol = 0;
-  if (!out || ngroups == 0 || kw_batch_last_pass(b, &rows, &npol) != KW_OK) return KW_E_ARG;
+  LastPass F(b, LastPass::kAnyPass);
+  if (!out || ngroups == 0 || !F.ok()) return KW_E_ARG;
+  const uint64_t rows = F.rows;
+  const uint32_t npol = F.npol;
   if (rows >> 32) return KW_E_ARG;  // (the sorted list holds u32 rows; a batch's offset columns are u32 too)
-  DeviceBatch& D = *b->dev;
+  DeviceBatch& D = *F.dev;
   const bool dbg = Knobs::on<KW_BULK_DEBUG>();
   const auto t_start = std::chrono::steady_clock::now();
   // the sorted row list and the unit table, then the rows as the device holds them
@@ -48,12 +41,11 @@ int batch_outcomes(kw_batch* b, const uint32_t* row_group, uint32_t ngroups, uin
   const uint64_t nunits = unit_at[nranges];
   if (nunits >> 32) return KW_E_ARG;
 
-  HIPCHK(hipSetDevice(D.device));
-  hipStream_t s = D.cur ? D.cur : D.stream;
+  if (int rc = F.open()) return rc;
+  hipStream_t s = F.s;
   const size_t b_order = (size_t)rows * 4, b_units = (size_t)nunits * sizeof(OutUnit);
   const size_t b_range = outcome_table_words((uint32_t)std::min<uint64_t>(per, ngroups), npol) * 8;
-  BlockLease dorder, dunits, dtable, hin, htable;
-  Drain drain{s};
+  BlockLease &dorder = F.lease(), &dunits = F.lease(), &dtable = F.lease(), &hin = F.lease(), &htable = F.lease();
   HIPCHK(hin.alloc(host_pool(), D.device, b_order + b_units));
   HIPCHK(htable.alloc(host_pool(), D.device, b_range));
   HIPCHK(dorder.alloc(dev_pool(), D.device, b_order));
@@ -98,10 +90,10 @@ int batch_outcomes(kw_batch* b, const uint32_t* row_group, uint32_t ngroups, uin
     memcpy(out + outcome_table_words(g0, npol), htable.p, bytes);
   }
   if (dbg) {
-    const std::chrono::duration<double, std::milli> sort = t_sorted - t_start, all = std::chrono::steady_clock::now() - t_start;
+    const std::chrono::duration<double, std::milli> sort = t_sorted - t_start;
     fprintf(stderr, "[kw outcomes] %llu rows x %u, %u groups in %u ranges, %llu units: sort and units %.3f ms on the host, "
             "zero + count %.3f ms on the device, the call %.3f ms\n", (unsigned long long)rows, npol, ngroups, nranges,
-            (unsigned long long)nunits, sort.count(), dev_ms, all.count());
+            (unsigned long long)nunits, sort.count(), dev_ms, ms_since(t_start));
   }
   return KW_OK;
 }

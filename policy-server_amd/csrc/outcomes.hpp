@@ -1,7 +1,7 @@
 // outcomes.hpp — the pure arithmetic of the grouped outcome count (include/kwgpu.h kw_batch_outcomes):
 // the 9-valued outcome of a verdict word, which is everything Metrics::record (metrics.cpp) reads
 // from it; the reference host reducer over words [rows][npol] and a group id per row; and the
-// geometry of the device count (kernels.hip outcomes_kernel): the counting sort of the rows by
+// geometry of the device count (reports.hip outcomes_kernel): the counting sort of the rows by
 // group, the unit table and the cut of the groups into ranges whose table fits a byte budget.
 // No HIP, no batch, no settings (tests/outcomes_check.cpp runs it on the host).
 //

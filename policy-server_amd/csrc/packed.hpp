@@ -2,7 +2,7 @@
 // code per (row, column) in two bit-planes per 64-column group, a dictionary of three words per
 // column, and the words the dictionary does not hold ("exceptions") in row-major order behind a
 // per-row offset. The dictionary, the array sizes, the reference host encoder, word(row, col) and
-// the expansion of a row range; the device pack kernels (kernels.hip) share the code function, the
+// the expansion of a row range; the device pack kernels (reports.hip) share the code function, the
 // item numbering and the wave geometry. No HIP, no batch, no settings (tests/packed_check.cpp runs
 // it on the host).
 #pragma once
@@ -58,7 +58,7 @@ KW_HD inline PackGeom pack_geom(uint32_t npol) {
   g.ipw = g.ipi * g.T;
   return g;
 }
-// The offsets scan (kernels.hip): a workgroup of 256 threads scans kScanPer counts per thread.
+// The offsets scan (reports.hip): a workgroup of 256 threads scans kScanPer counts per thread.
 constexpr uint32_t kScanPer = 4, kScanBlock = 256 * kScanPer;
 
 KW_HD inline uint32_t packed_popc(uint64_t x) { return (uint32_t)__builtin_popcountll(x); }

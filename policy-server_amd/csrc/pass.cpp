@@ -9,6 +9,7 @@
 #include <memory>
 
 #include "knobs.hpp"
+#include "lastpass.hpp"
 #include "plan.hpp"
 
 namespace kw {
@@ -717,7 +718,6 @@ int read_verdicts(kw_batch* b, uint32_t* host_out, size_t count) {
   HIPCHK(hipSetDevice(D.device));
   hipStream_t s = D.cur ? D.cur : D.stream;
   const size_t vbytes = count * sizeof(uint32_t);
-  constexpr size_t kBounce = (size_t)64 << 20;
   {
     // (the bounce block returns to the pool on the error returns too: each one precedes the
     // enqueue or follows a failed enqueue or synchronise)
@@ -743,13 +743,7 @@ int read_verdicts(kw_batch* b, uint32_t* host_out, size_t count) {
     } else if (vbytes > ((size_t)16 << 20)) {
       // large read-backs through a pinned bounce block (full-rate DMA), fanned out to the caller's
       // (pageable) buffer by several threads
-      HIPCHK(bounce.alloc(host_pool(), D.device, kBounce));
-      for (size_t at = 0; at < vbytes; at += kBounce) {
-        const size_t n = std::min(kBounce, vbytes - at);
-        HIPCHK(hipMemcpyAsync(bounce.p, (const uint8_t*)D.verdicts + at, n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        parallel_copy((uint8_t*)host_out + at, bounce.p, n);
-      }
+      if (int rc = bounce_read(bounce, D.device, s, host_out, D.verdicts, vbytes)) return rc;
     } else if (count) {
       HIPCHK(hipMemcpyAsync(host_out, D.verdicts, vbytes, hipMemcpyDeviceToHost, s));
     }

@@ -1,53 +1,34 @@
 // summary.cpp — the summary form's entries on a resident pass (include/kwgpu.h): kw_batch_summary
 // reduces the last pass's verdict words on the device and reads back the counters and the planes;
 // kw_batch_verdict_rows gathers the words of chosen rows, sized by kw_batch_last_pass; the
-// host-reducer diagnostic. The arithmetic is summary.hpp's, the kernels kernels.hip's, the bulk
+// host-reducer diagnostic. The arithmetic is summary.hpp's, the kernels reports.hip's, the bulk
 // pass bulk.cpp's, its summary form bulkout.cpp's.
 #include "summary.hpp"
 
 #include <cstdio>
 #include <cstring>
 
-#include "kernels.hpp"
 #include "knobs.hpp"
-#include "pass.hpp"
+#include "lastpass.hpp"
+#include "reports.hpp"
 #include "upload.hpp"
 
 namespace kw {
-
-// The rows of the last pass and its words per row; false when the batch holds no pass.
-static bool last_pass(const kw_batch* b, uint64_t* rows, uint32_t* rw) {
-  if (!b || !b->dev || b->dev->device < 0) return false;
-  const DeviceBatch& D = *b->dev;
-  if (!D.last_row_words || !D.verdicts) return false;
-  *rw = D.last_row_words;
-  *rows = D.last_verdicts / D.last_row_words;
-  return true;
-}
-
 namespace {
 
-// Declared after the leases a call holds: the stream is drained before any block returns to its pool,
-// on the error returns too.
-struct Drain {
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 int batch_summary(kw_batch* b, kw_summary* out) {
-  uint64_t rows = 0;
-  uint32_t npol = 0;
-  if (!out || !out->col || !last_pass(b, &rows, &npol)) return KW_E_ARG;
+  LastPass F(b, LastPass::kAnyPass);
+  if (!out || !out->col || !F.ok()) return KW_E_ARG;
+  const uint64_t rows = F.rows;
+  const uint32_t npol = F.npol;
   if (out->rows != rows || out->npol != npol) return KW_E_ARG;
-  DeviceBatch& D = *b->dev;
-  HIPCHK(hipSetDevice(D.device));
-  hipStream_t s = D.cur ? D.cur : D.stream;
+  DeviceBatch& D = *F.dev;
+  if (int rc = F.open()) return rc;
+  hipStream_t s = F.s;
   const uint32_t G = packed_groups(npol);
   const size_t b_tot = summary_col_words(npol) * 8, b_planes = (size_t)rows * G * 16;
   const bool planes = out->planes && rows;
-  constexpr size_t kBounce = (size_t)64 << 20;
-  BlockLease dtot, dpart, dplanes, htot, bounce;
-  Drain drain{s};
+  BlockLease &dtot = F.lease(), &dpart = F.lease(), &dplanes = F.lease(), &htot = F.lease(), &bounce = F.lease();
   HIPCHK(dtot.alloc(dev_pool(), D.device, b_tot));
   HIPCHK(htot.alloc(host_pool(), D.device, b_tot));
   HIPCHK(dpart.alloc(dev_pool(), D.device, std::max<size_t>(summary_part_bytes(rows, npol), 256)));
@@ -67,24 +48,22 @@ int batch_summary(kw_batch* b, kw_summary* out) {
   HIPCHK(hipMemcpyAsync(htot.p, dtot.p, b_tot, hipMemcpyDeviceToHost, s));
   if (planes && !D.split && page_locked(out->planes)) {
     HIPCHK(hipMemcpyAsync(out->planes, dplanes.p, b_planes, hipMemcpyDeviceToHost, s));
+  } else if (planes && !D.split) {
+    if (int rc = bounce_read(bounce, D.device, s, out->planes, dplanes.p, b_planes)) return rc;
   } else if (planes) {
-    // through a pinned bounce block; a split batch holds its rows in device order: each row's plane
-    // words go to its batch row (read_verdicts does the same for words)
+    // a split batch holds its rows in device order: through the bounce block by whole rows, each
+    // row's plane words to its batch row (read_verdicts does the same for words)
     const size_t rb = (size_t)G * 16, per = std::max<size_t>(1, kBounce / rb);
     HIPCHK(bounce.alloc(host_pool(), D.device, std::min(kBounce, std::max<size_t>(b_planes, rb))));
     for (uint64_t d0 = 0; d0 < rows; d0 += per) {
       const uint64_t d1 = std::min<uint64_t>(rows, d0 + per);
       HIPCHK(hipMemcpyAsync(bounce.p, (const uint8_t*)dplanes.p + d0 * rb, (d1 - d0) * rb, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
-      if (!D.split) {
-        parallel_copy((uint8_t*)out->planes + d0 * rb, bounce.p, (d1 - d0) * rb);
-      } else {
-        const uint8_t* src = (const uint8_t*)bounce.p;
-        HostWorkers::get().run((size_t)((d1 - d0 + 4095) / 4096), [&](size_t q) {
-          for (uint64_t d = d0 + q * 4096, e = std::min(d1, d0 + (q + 1) * 4096); d < e; ++d)
-            memcpy((uint8_t*)out->planes + D.perm[d] * rb, src + (d - d0) * rb, rb);
-        });
-      }
+      const uint8_t* src = (const uint8_t*)bounce.p;
+      HostWorkers::get().run((size_t)((d1 - d0 + 4095) / 4096), [&](size_t q) {
+        for (uint64_t d = d0 + q * 4096, e = std::min(d1, d0 + (q + 1) * 4096); d < e; ++d)
+          memcpy((uint8_t*)out->planes + D.perm[d] * rb, src + (d - d0) * rb, rb);
+      });
     }
   }
   HIPCHK(hipStreamSynchronize(s));
@@ -96,19 +75,19 @@ int batch_summary(kw_batch* b, kw_summary* out) {
 }
 
 int batch_verdict_rows(kw_batch* b, const uint64_t* rows, size_t n, uint32_t* out) {
-  uint64_t nrows = 0;
-  uint32_t rw = 0;
-  if (!last_pass(b, &nrows, &rw) || (n && (!rows || !out))) return KW_E_ARG;
+  LastPass F(b, LastPass::kAnyPass);
+  if (!F.ok() || (n && (!rows || !out))) return KW_E_ARG;
+  const uint64_t nrows = F.rows;
+  const uint32_t rw = F.npol;
   for (size_t i = 0; i < n; ++i)
     if (rows[i] >= nrows) return KW_E_ARG;
   if (n == 0) return KW_OK;
-  DeviceBatch& D = *b->dev;
-  HIPCHK(hipSetDevice(D.device));
-  hipStream_t s = D.cur ? D.cur : D.stream;
+  DeviceBatch& D = *F.dev;
+  if (int rc = F.open()) return rc;
+  hipStream_t s = F.s;
   if (D.split) D.device_rows();
   const size_t b_idx = n * 8, b_out = n * (size_t)rw * 4;
-  BlockLease didx, dout, hidx, hout;
-  Drain drain{s};
+  BlockLease &didx = F.lease(), &dout = F.lease(), &hidx = F.lease(), &hout = F.lease();
   HIPCHK(hidx.alloc(host_pool(), D.device, b_idx));
   HIPCHK(hout.alloc(host_pool(), D.device, b_out));
   HIPCHK(didx.alloc(dev_pool(), D.device, b_idx));
@@ -143,11 +122,6 @@ int kw_validate_host_summary(const kw_env* env, kw_batch* b, const int32_t* poli
 
 int kw_batch_verdict_rows(kw_batch* b, const uint64_t* rows, size_t n, uint32_t* out) {
   return kw::batch_verdict_rows(b, rows, n, out);
-}
-
-int kw_batch_last_pass(const kw_batch* b, uint64_t* rows, uint32_t* row_words) {
-  if (!rows || !row_words) return KW_E_ARG;
-  return kw::last_pass(b, rows, row_words) ? KW_OK : KW_E_ARG;
 }
 
 int kw_debug_summarize_words(const uint32_t* words, uint64_t rows, uint32_t npol, kw_summary* out) {

@@ -1,7 +1,7 @@
 // summary.hpp — the pure arithmetic of the summary form (include/kwgpu.h kw_summary): per-column
 // counters of a pass's verdict words and two bit-planes per 64-column group that mark the pairs worth
 // a message. The bucket and bit functions, the reference host reducer, and the geometry of the
-// reduction kernels (kernels.hip summary_kernel): which (row, column) a lane reads in which round,
+// reduction kernels (reports.hip summary_kernel): which (row, column) a lane reads in which round,
 // the grid, and the cap that keeps the u32 partial counters from wrapping. The device kernels share
 // all of it. No HIP, no batch, no settings (tests/summary_check.cpp runs it on the host).
 //

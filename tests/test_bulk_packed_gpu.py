@@ -75,6 +75,10 @@ def _both_outputs(name, scfg, rows, seed, ids, chunk, origin=K.VALIDATE):
     ("c3_group", 3, 20000, 4096),   # 4 columns: 16 rows per wave round
     ("parity", 0, 20000, 1500),
     ("c4_64", 4, 30011, 2048),      # rows off every wave's and workgroup's span
+    # one column, 256 * 1024 + 1 items in one chunk: 257 block sums, so the one-workgroup scan over
+    # them takes a second round of 256. The first chunk of a pass is a sixteenth of chunk_rows
+    # (bulkplan.hpp chunk_bounds), so 16 times the rows, rounded up to whole tiles, keeps them together
+    ("c2_trusted", 2, 262145, 16 * 262208),
 ])
 def test_packed_chunked_matches_oracle_and_host_encoder(name, scfg, rows, chunk):
     env, _ = _envs(name)

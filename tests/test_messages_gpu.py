@@ -74,8 +74,8 @@ def _c4(rows):
     return env, ids, b, words
 
 
-@pytest.mark.parametrize("count", [1, 63, 64, 65, 257, "all", "shuffled"])
-def test_item_counts(count):
+@pytest.mark.parametrize("count", [1, 63, 64, 65, 257, 4096, 4097, "all", "shuffled"])
+def test_item_counts(count):  # (4096: the scan's tile of lengths exactly full; 4097: one length into a second tile)
     env, ids, b, words = _c4(3000)
     rows, cols, nf = items_of(words, len(ids), extra=0)
     assert nf > 20000
