@@ -18,7 +18,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -munsafe-fp-atomic
 
 HOST_SRCS := json yaml automaton expr env flatten service slotplan metrics knobs pools plan pass upload bulk bulkout packed lastpass summary outcomes digest members messages capi
 HOST_OBJS := $(addprefix $(OBJ)/,$(addsuffix .o,$(HOST_SRCS)))
-HEADERS := $(wildcard $(SRC)/*.hpp) include/kwgpu.h
+# the device objects: the hot path (kernels.hip), the reports over its verdict words (reports.hip)
+# and the wide path's combine kernel with the group programs' VM (groups.hip)
+DEV_SRCS := kernels reports groups
+DEV_OBJS := $(addprefix $(OBJ)/,$(addsuffix .o,$(DEV_SRCS)))
+VOBJ = $(PKG)/variants/obj-$(NAME)
 
 all: $(PKG)/libkwgpu.so $(PKG)/libkwsynth.so $(PKG)/kwhost $(PKG)/kwload oracle/build/libkworacle.so scripts/lds_calib scripts/lds_occ scripts/fmt_bench
 
@@ -34,16 +38,20 @@ scripts/lds_calib: scripts/lds_calib.hip
 scripts/lds_occ: scripts/lds_occ.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -o $@ $<
 
-$(OBJ)/%.o: $(SRC)/%.cpp $(HEADERS)
+# every object depends on the headers it includes, as the compiler lists them (build/*.d). An
+# object left by a build that wrote no list (this Makefile before DEV_SRCS) has none: run
+# `make clean` once over such a build/, or header edits will not reach those objects.
+$(OBJ)/%.o: $(SRC)/%.cpp
 	@mkdir -p $(OBJ)
-	$(CXX) $(CXXFLAGS) -c $< -o $@
+	$(CXX) $(CXXFLAGS) -MMD -MP -c $< -o $@
 
-# the device objects: the hot path (kernels.hip) and the reports over its verdict words (reports.hip)
-$(OBJ)/kernels.o $(OBJ)/reports.o: $(OBJ)/%.o: $(SRC)/%.hip $(HEADERS)
+$(DEV_OBJS): $(OBJ)/%.o: $(SRC)/%.hip
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
 
-$(PKG)/libkwgpu.so: $(HOST_OBJS) $(OBJ)/kernels.o $(OBJ)/reports.o
+-include $(HOST_OBJS:.o=.d) $(DEV_OBJS:.o=.d)
+
+$(PKG)/libkwgpu.so: $(HOST_OBJS) $(DEV_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 $(PKG)/kwhost: $(SRC)/kwhost.cpp include/kwgpu.h $(PKG)/libkwgpu.so
@@ -63,25 +71,26 @@ oracle/build/libkworacle.so: oracle/kworacle.c oracle/kwregex.c oracle/kworacle.
 # -> policy-server_amd/variants/x.so (KWGPU_LIB selects it; scripts/ab.sh benches every variant);
 # KSRC=<file in csrc/> builds another kernels source in place of kernels.hip (e.g. the previous commit's)
 variant: $(HOST_OBJS)
-	@mkdir -p $(PKG)/variants/obj-$(NAME)
-	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(or $(KSRC),$(SRC)/kernels.hip) -o $(PKG)/variants/obj-$(NAME)/kernels.o
-	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(SRC)/reports.hip -o $(PKG)/variants/obj-$(NAME)/reports.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(HOST_OBJS) $(PKG)/variants/obj-$(NAME)/kernels.o $(PKG)/variants/obj-$(NAME)/reports.o
+	@mkdir -p $(VOBJ)
+	for f in $(DEV_SRCS); do src=$(SRC)/$$f.hip; [ $$f = kernels ] && src=$(or $(KSRC),$(SRC)/kernels.hip); \
+	  $(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $$src -o $(VOBJ)/$$f.o || exit 1; done
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(HOST_OBJS) $(addprefix $(VOBJ)/,$(addsuffix .o,$(DEV_SRCS)))
 
 # A/B variant built entirely (host engine + kernels) from another source directory next to csrc/,
 # e.g. a snapshot of an earlier commit: make variant-full NAME=x VSRC=policy-server_amd/csrc_x
+# (of the device sources, those the snapshot has: an earlier commit may hold fewer)
 variant-full:
-	@mkdir -p $(PKG)/variants/obj-$(NAME)
-	for f in $(HOST_SRCS); do $(CXX) $(CXXFLAGS) $(VFLAGS) -c $(VSRC)/$$f.cpp -o $(PKG)/variants/obj-$(NAME)/$$f.o || exit 1; done
-	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(VSRC)/kernels.hip -o $(PKG)/variants/obj-$(NAME)/kernels.o
-	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(VSRC)/reports.hip -o $(PKG)/variants/obj-$(NAME)/reports.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(addprefix $(PKG)/variants/obj-$(NAME)/,$(addsuffix .o,$(HOST_SRCS))) $(PKG)/variants/obj-$(NAME)/kernels.o $(PKG)/variants/obj-$(NAME)/reports.o
+	@mkdir -p $(VOBJ)
+	for f in $(HOST_SRCS); do $(CXX) $(CXXFLAGS) $(VFLAGS) -c $(VSRC)/$$f.cpp -o $(VOBJ)/$$f.o || exit 1; done
+	objs=; for f in $(DEV_SRCS); do [ -f $(VSRC)/$$f.hip ] || continue; \
+	  $(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $(VSRC)/$$f.hip -o $(VOBJ)/$$f.o || exit 1; objs="$$objs $(VOBJ)/$$f.o"; done; \
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(PKG)/variants/$(NAME).so $(addprefix $(VOBJ)/,$(addsuffix .o,$(HOST_SRCS))) $$objs
 
 # kernel resource usage (VGPR/SGPR/LDS/occupancy) report
-resources: $(SRC)/kernels.hip $(SRC)/reports.hip
+resources: $(addprefix $(SRC)/,$(addsuffix .hip,$(DEV_SRCS)))
 	for f in $^; do $(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $$f -o /dev/null || exit 1; done
 
 clean:
 	rm -rf $(OBJ) $(PKG)/*.so $(PKG)/kwhost $(PKG)/kwload oracle/build
 
-.PHONY: all clean resources variant
+.PHONY: all clean resources variant variant-full

@@ -105,7 +105,7 @@ struct WideData {
   uint32_t nwide = 0;
   std::vector<int32_t> wide_policy;  // wide index -> group policy (all-pairs mode)
   bool rows_mode = false;
-  // cause bitsets of wide groups (> 64 members or deep stacks, kernels.hpp WideGroupPass):
+  // cause bitsets of wide groups (> 64 members or deep stacks, groups.hpp WideGroupPass):
   // [row][big_stride] u64, the group `policy` at words [off, off + words) of its row
   struct BigRef {
     int32_t policy;

@@ -17,6 +17,8 @@
 #include "batch.hpp"
 #include "devbatch.hpp"
 #include "env.hpp"
+#include "groups.hpp"
+#include "groupvm.hpp"
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "metrics.hpp"

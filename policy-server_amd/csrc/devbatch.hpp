@@ -14,6 +14,7 @@
 #include "batch.hpp"
 #include "digest.hpp"
 #include "env.hpp"
+#include "groups.hpp"
 #include "kernels.hpp"
 #include "pools.hpp"
 #include "slotplan.hpp"

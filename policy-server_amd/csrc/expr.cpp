@@ -1,7 +1,7 @@
 // expr.cpp — see expr.hpp. Lexer, recursive-descent parser with rhai's precedence, a host
 // interpreter (validation, response messages, truth tables), constant folding of call-free
 // subtrees, and the device forms: short-circuit jump code, a truth table, or script bytecode
-// (kwdev.hpp SOp) for the typed stack machine of slots.hpp.
+// (kwdev.hpp SOp) for the typed stack machine of groupvm.hpp.
 #define KW_PLANNING_TU  // (knobs.hpp: PlanKnobs only)
 #include "expr.hpp"
 
@@ -1143,7 +1143,7 @@ std::string str_case(const std::string& s, bool upper) {
   return utf8_of(o);
 }
 // rhai's checked ** << >> on i64: a negative shift shifts the other way; 64 or more bits, an exponent
-// outside [0, u32::MAX] or a power past i64 is an error; >> is arithmetic (slots.hpp int_pow_shift
+// outside [0, u32::MAX] or a power past i64 is an error; >> is arithmetic (groupvm.hpp run_script_prog
 // is the device form)
 bool int_pow_shift(const std::string& op, int64_t x, int64_t y, int64_t* r, std::string* err) {
   const std::string ex = std::to_string(x) + " " + op + " " + std::to_string(y);
@@ -1351,7 +1351,7 @@ struct Interp {
       if (vars[k].first == name) return &vars[k].second;
     return nullptr;
   }
-  // deep equality: 1 / 0, -1 past kMaxCompareDepth (slots.hpp veq walks in the same order)
+  // deep equality: 1 / 0, -1 past kMaxCompareDepth (groupvm.hpp veq walks in the same order)
   int eq(const Val& a, const Val& b, uint32_t d) const {
     if (a.t != b.t) return 0;
     switch (a.t) {
@@ -1406,7 +1406,7 @@ struct Interp {
 
   // A built-in over its arguments a (a[0] by value: the function changes it in place when rhai's
   // takes `&mut`, and the caller stores it back for a method-style call on a variable). Charges
-  // against kMaxScriptAlloc (slots.hpp charges the same): a new string its bytes, a new or copied
+  // against kMaxScriptAlloc (groupvm.hpp charges the same): a new string its bytes, a new or copied
   // array 16 B a cell; slices (sub_string, trim, split pieces, extract, pop, ...) are free.
   Flow builtin(int fid, const std::string& name, std::vector<Val>& a, Val* out) {
     std::vector<const Val*> ap;

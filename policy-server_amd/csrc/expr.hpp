@@ -29,7 +29,7 @@
 //              separate pass and a combine kernel runs the jump code (u16 member operands, stack in
 //              global scratch) over their verdict words;
 //   script     anything else with more than 16 members: the same separate member pass, and the
-//              combine kernel runs typed bytecode (slots.hpp run_script_prog: (), bool, i64 and
+//              combine kernel runs typed bytecode (groupvm.hpp run_script_prog: (), bool, i64 and
 //              string values, `let` slots, rhai's checked arithmetic; the host interpreter words the
 //              messages). No member count is refused.
 #pragma once

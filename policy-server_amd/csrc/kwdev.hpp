@@ -58,7 +58,7 @@ enum PolicyFlag : uint8_t {
 //                           G_JT / G_JF targets are u32
 enum GOp : uint8_t { G_CONST0 = 0, G_CONST1 = 1, G_CALL = 2, G_NOT = 3, G_JT = 4, G_JF = 5, G_EQ = 6, G_NE = 7, G_CALL16 = 8 };
 // Script bytecode (groups beyond the bool-only subset that no truth table covers; expr.cpp emits
-// it, slots.hpp run_script_prog runs it). Header (32 B): u32 depth (value stack bound), nvars
+// it, groupvm.hpp run_script_prog runs it). Header (32 B): u32 depth (value stack bound), nvars
 // (variable slots of every frame a run can hold), arena (bytes of strings and arrays a run may
 // build), code_len, nframes (script-function frames: 0 or kMaxCallDepth), type_of names offset,
 // char table offset and entry count; then the code, then the string pool, then the char table.

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <memory>
 
+#include "groups.hpp"
 #include "knobs.hpp"
 #include "lastpass.hpp"
 #include "plan.hpp"

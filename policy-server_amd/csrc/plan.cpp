@@ -9,6 +9,8 @@
 #include <cstring>
 #include <map>
 
+#include "groups.hpp"
+#include "groupvm.hpp"
 #include "knobs.hpp"
 #include "slots.hpp"
 

@@ -2,7 +2,7 @@
 "What's missing" 1). Each row states what rhai 1.21.0 answers (upstream policy-evaluator v0.24.0,
 Cargo.lock:5116-5118, run by evaluation_environment.rs:587-651), written from the language's
 documented semantics, not from either implementation here: it is the independent pin the product
-(expr.cpp, slots.hpp) and the oracle (oracle/rhaisub.py) are both checked against. rhai itself cannot
+(expr.cpp, groupvm.hpp) and the oracle (oracle/rhaisub.py) are both checked against. rhai itself cannot
 run in this image, so rows that no reference-held vector covers are parity unpinned.
 
 Members a, b, c are safe-labels policies with one mandatory label each ("a", "b", "c"): a request

@@ -1,6 +1,6 @@
 """Group scripts beyond the bool-only subset with more than 16 members (VERDICT r03 "What's
 missing" 3): `let` / `if` / integers / strings over 40 members compile to typed bytecode (kwdev.hpp
-SOp) that the wide path's combine kernel runs per row (slots.hpp run_script_prog); the oracle
+SOp) that the wide path's combine kernel runs per row (groupvm.hpp run_script_prog); the oracle
 evaluates them with its own interpreter (oracle.py run_script) over the members' own results.
 CPU: the product's host walk of that bytecode against the oracle, words and responses."""
 import random

@@ -3,7 +3,7 @@ arrays, `in`, switch, `??`, methods, compound assignment, loops, functions, and 
 engine refuses by name. Three-way: the hand-written rhai expectations of tests/rhai_cases.py (the
 independent pin), the oracle's interpreter (oracle/rhaisub.py) and the product (expr.cpp) — through
 the slot compiler's host walk in both device forms the product uses for such groups: the truth
-table, and (KW_GROUP_FORM=script) the typed bytecode of slots.hpp run_script_prog.
+table, and (KW_GROUP_FORM=script) the typed bytecode of groupvm.hpp run_script_prog.
 Reference: evaluation_environment.rs:587-651 (group evaluation), :979-1042 (causes); the language is
 upstream rhai 1.21.0 (Cargo.lock:5116-5118), parity beyond the pinned vectors unpinned."""
 import json

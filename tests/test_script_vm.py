@@ -1,0 +1,57 @@
+"""The wide path's group programs (policy-server_amd/csrc/groupvm.hpp: the script VM and the wide
+jump code) alone on the host. tests/script_check.cpp compiles each script for the wide path, runs
+it for every vector of member results in heap blocks of exactly the sizes the planner gives the
+device, and compares each run with the host interpreter; it runs as a plain executable under
+AddressSanitizer and UBSan (no Python in that process). The scripts are the expressions of
+rhai_cases.VALID and 3 seeds x 60 scripts of fuzz._script over the members a, b, c."""
+import os
+import random
+import re
+import shutil
+import subprocess
+
+from fuzz import _script
+from rhai_cases import VALID
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "policy-server_amd", "csrc")
+CXX = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
+MEMBERS = ["a", "b", "c"]
+SEEDS = (9000, 9001, 9002)
+
+
+def scripts():
+    rows = [expr for expr, _ in VALID]
+    for seed in SEEDS:
+        rng = random.Random(seed)
+        rows += [_script(rng, MEMBERS) for _ in range(60)]
+    return rows
+
+
+def test_script_check_under_sanitizers(tmp_path):
+    rows = scripts()
+    src = tmp_path / "scripts.bin"
+    with open(src, "wb") as f:
+        f.write(b"%d\n" % len(rows))
+        for expr in rows:
+            body = expr.encode()
+            f.write(b"%d %d\n%s\n" % (len(MEMBERS), len(body), " ".join(MEMBERS).encode()))
+            f.write(body + b"\n")
+    exe = tmp_path / "script_check"
+    subprocess.run([CXX, "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__", "-I", CSRC, "-o", str(exe),
+                    os.path.join(ROOT, "tests", "script_check.cpp"), os.path.join(CSRC, "expr.cpp"),
+                    os.path.join(CSRC, "knobs.cpp")], check=True)
+    # (out-of-bounds accesses and undefined behaviour are the point; the leak check at exit needs
+    # ptrace rights a test runner may lack)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    env.pop("KW_GROUP_FORM", None)  # the form is the compiler's own choice for the wide path
+    out = subprocess.run([str(exe), str(src)], check=False, capture_output=True, text=True, env=env)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    m = re.search(r"scripts (\d+) vm (\d+) wide (\d+) refused (\d+) runs (\d+) failures (\d+)", out.stdout)
+    assert m, out.stdout[-3000:]
+    n, vm, wide, refused, runs, failures = map(int, m.groups())
+    print(out.stdout.strip())
+    assert failures == 0 and n == len(rows)
+    assert 2 * vm >= n, "fewer than half of the scripts reached the script VM"
+    assert runs == (vm + wide) * (1 << len(MEMBERS))

@@ -1,6 +1,6 @@
 """Policies beyond one slot-plan chunk's 64 local bits (VERDICT r03 "What's missing" 4): more than
 64 distinct mandatory labels, more than 63 required-drop / default-add capabilities. The product
-evaluates them as hidden parts combined on the wide path (env.cpp split_policy, kernels.hpp
+evaluates them as hidden parts combined on the wide path (env.cpp split_policy, groups.hpp
 combine_parts); the oracle has no such limit. CPU: the host walk against the oracle."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
 """CPU: policy groups past the jump-code limits: more than 64 members, and
 value stacks deeper than 64 (== / != nesting). Such a group's members run as a separate pass and
-its expression runs over their verdict words (expr.hpp "wide"; kernels.hip wide_groups_kernel).
+its expression runs over their verdict words (expr.hpp "wide"; groups.hip wide_groups_kernel).
 Here: the slot compiler's host walk (kw_debug_host_walk, the same jump code on the host) against
 the oracle's recursive evaluation, bit-exact, in both origins. The reference builds a group over
 any number of members (evaluation_environment.rs:613-648, config.rs:386-388). The GPU twin, with
