@@ -722,6 +722,54 @@ int kw_debug_messages_words(const kw_env *env, const kw_batch *b, const int32_t 
  * host, and whether that call uploaded the container names (1 / 0). KW_E_ARG for a batch that never
  * ran the call. */
 int kw_debug_messages_stats(const kw_batch *b, uint64_t *out);
+/* Where the audit flow ends: the whole AdmissionResponse bodies of chosen pairs, rendered on the
+ * device. Response i is, byte for byte, what kw_format_response(env, b, rows[i], policies[cols[i]],
+ * w, mv, ...) writes, w the pass's word at the pair and, for a group, mv[s] the pass's word at
+ * (rows[i], c_s), c_s the first column with policies[c_s] equal to the group's member s: the uid echo,
+ * `allowed`, status.message JSON-escaped, `code`, and a group's details.causes with the field and the
+ * message of every rejecting member ("mutation is not allowed inside of policy group" for a member
+ * that is allowed and mutated). Strings are escaped exactly as the host formatter escapes them: the
+ * quote, the backslash, \n \r \t \b \f in two bytes, any other byte below 0x20 as \u00xx in lower-case
+ * hex, every other byte unchanged (invalid UTF-8 included). The fields, the capacities, KW_E_NOSPACE
+ * (bytes, nhost and all of off exact), the argument errors, any order and repeats of items, batch
+ * rows for a split batch, page-locked or pageable `text`, the same bytes for the same input and
+ * "leaves the batch good for further calls" are word for word kw_batch_messages' contract. The items
+ * in `host` have a zero-length response here and are left to kw_format_response(_doc):
+ *   every item for which kw_format_response answers an error instead of a response (KW_F_PATCH, an
+ *   unregistered policy on the bypass path, a group with a broken member); reason KW_R_GROUP_EXPR; a
+ *   word of reason 1-12 whose ARG is KW_ARG_WIDE; a group word whose ARG is KW_ARG_WIDE (more than 15
+ *   members); a group with a member that is no column of the pass; a group with a cause whose own
+ *   message is left to the host by these rules; an argument the request does not hold.
+ * The uid column, like the container names, is uploaded from the host batch by the first call and
+ * kept until the batch is uploaded again or destroyed. The items run in rounds of at most
+ * KW_MESSAGES_CHUNK, the text through windows of KW_MESSAGES_WINDOW bytes. kw_batch_messages and its
+ * bytes are unchanged by this call. Synchronises with the pass's stream. Replaces one
+ * kw_format_response per pair (service::evaluate's response building). */
+typedef struct kw_responses {   /* the fields of kw_messages, same meaning */
+  uint64_t *off;
+  char *text;
+  size_t cap;
+  size_t bytes;
+  uint32_t *words;
+  uint64_t *host;
+  size_t host_cap, nhost;
+} kw_responses;
+int kw_batch_responses(kw_batch *b, const kw_env *env, const int32_t *policies, uint32_t npol,
+                       const uint64_t *rows, const uint32_t *cols, size_t n, kw_responses *out);
+/* Diagnostic (tests, documents): the same output on the host from full words [nrows][npol] (nrows <=
+ * the batch's) and the host batch; the members' words are read from the same matrix. how = 0: one
+ * format_response per item, the reference (an item it answers an error for is listed in host instead
+ * of failing the call); how = 1: the part and piece renderer the device runs (csrc/responses.hpp),
+ * over the host columns. */
+int kw_debug_responses_words(const kw_env *env, const kw_batch *b, const int32_t *policies, uint32_t npol,
+                             const uint32_t *words, uint64_t nrows, const uint64_t *rows,
+                             const uint32_t *cols, size_t n, int how, kw_responses *out);
+/* Diagnostic (tests): what the batch's last kw_batch_responses did. out[0..6): the rounds, the
+ * staging windows written, the responses that spanned more than one window, the items listed for
+ * the host, whether that call uploaded a side column (the uid column or the container names; 1 / 0),
+ * and the pieces whose escaped length exceeded their raw length. KW_E_ARG for a batch that never ran
+ * the call. */
+int kw_debug_responses_stats(const kw_batch *b, uint64_t *out);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes

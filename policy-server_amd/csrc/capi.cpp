@@ -839,6 +839,20 @@ int kw_debug_messages_words(const kw_env* env, const kw_batch* b, const int32_t*
 
 int kw_debug_messages_stats(const kw_batch* b, uint64_t* out) { return debug_messages_stats(b, out); }
 
+int kw_batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uint32_t npol, const uint64_t* rows,
+                       const uint32_t* cols, size_t n, kw_responses* out) {
+  if (!b || !env || !out || (npol && !policies)) return KW_E_ARG;
+  return batch_responses(b, env, policies, npol, rows, cols, n, out);
+}
+
+int kw_debug_responses_words(const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol, const uint32_t* words,
+                             uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int how, kw_responses* out) {
+  if (!b || !env || !out || (npol && !policies)) return KW_E_ARG;
+  return debug_responses_words(env, b, policies, npol, words, nrows, rows, cols, n, how, out);
+}
+
+int kw_debug_responses_stats(const kw_batch* b, uint64_t* out) { return debug_responses_stats(b, out); }
+
 int kw_validate_timed(const kw_env* env, kw_batch* b, const int32_t* policies, uint32_t npol, int origin, int warmup,
                       int reps, kw_timing* out) {
   return validate_timed(env, b, policies, npol, origin, warmup, reps, out);

@@ -221,6 +221,16 @@ struct DeviceBatch {
   // spanned a window, items left to the host, whether it uploaded the names
   bool messages_ran = false;
   uint64_t messages_stats[5] = {0, 0, 0, 0, 0};
+  // the uid column (kw_batch_responses uploads it on first use, as the names are), in device-row
+  // order: one block [offsets | bytes and their zero tail]
+  uint8_t* uids = nullptr;
+  size_t uids_bytes = 0;
+  DCol uid_col;
+  // the last kw_batch_responses (kw_debug_responses_stats): rounds, windows written, responses that
+  // spanned a window, items left to the host, whether it uploaded a side column, pieces that grew by
+  // escaping
+  bool responses_ran = false;
+  uint64_t responses_stats[6] = {0, 0, 0, 0, 0, 0};
   // tile capacities of this batch (plan_pass), per tile height tried
   struct RowsPlan {
     uint32_t rows = 0;
@@ -246,6 +256,7 @@ struct DeviceBatch {
     P.release(device, overflow, overflow_cap * 4);
     P.release(device, cols, cols_bytes);
     P.release(device, names, names_bytes);
+    P.release(device, uids, uids_bytes);
     P.release(device, verdicts, verdict_cap * 4);
     P.release(device, g_cls, g_cls_cap * 2);
     P.release(device, nfa_cls, nfa_cls_cap * 2);

@@ -128,5 +128,16 @@ int batch_messages(kw_batch* b, const kw_env* env, const int32_t* policies, uint
 int debug_messages_words(const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol, const uint32_t* words,
                          uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int how, kw_messages* out);
 int debug_messages_stats(const kw_batch* b, uint64_t* out);
+// The container names to the device on stream s (DeviceBatch::names; the messages and the responses
+// upload them on first use).
+int upload_names(kw_batch* kb, hipStream_t s);
+
+// The AdmissionResponse bodies of chosen pairs (responses.cpp): kw_batch_responses over the last
+// all-pairs pass, and the host renderers and the statistics of the diagnostics.
+int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uint32_t npol, const uint64_t* rows,
+                    const uint32_t* cols, size_t n, kw_responses* out);
+int debug_responses_words(const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol, const uint32_t* words,
+                          uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int how, kw_responses* out);
+int debug_responses_stats(const kw_batch* b, uint64_t* out);
 
 }  // namespace kw

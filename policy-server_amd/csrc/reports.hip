@@ -867,4 +867,100 @@ hipError_t launch_messages_write(const MessagesArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- the response bodies of chosen pairs (reports.hpp ResponsesArgs, responses.hpp) -----------------
+
+__device__ inline RspCtx responses_ctx(const ResponsesArgs& a) {
+  RspCtx X;
+  X.C = a.cols;
+  X.uid = a.uid;
+  X.S = rsp_settings(a.settings);
+  X.words = a.words;
+  X.npol = a.npol;
+  return X;
+}
+
+__global__ void __launch_bounds__(256) responses_len_kernel(ResponsesArgs a) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  const uint64_t row = a.drow[i];
+  const uint32_t col = a.col[i];
+  uint32_t word = 0, st = RSP_TEXT, len = 0, nesc = 0;
+  if (row < a.cols.c.rows && col < a.npol) {  // (the host checked both: nothing is read outside the pass)
+    const RspCtx X = responses_ctx(a);
+    word = a.words[row * a.npol + col];
+    RspItem it;
+    st = col < X.S.ncols ? rsp_item(X.S, col, word, &it) : (uint32_t)RSP_HOST;
+    if (st == RSP_TEXT) st = rsp_measure(X, row, col, word, it, &len, &nesc);
+  }
+  a.len[i] = st == RSP_TEXT ? len : 0u;
+  a.mark[i] = st == RSP_HOST ? 1u : 0u;
+  if (a.out_words) a.out_words[i] = word;
+  if (st == RSP_MISSING) __hip_atomic_store(&a.head->missing, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (st == RSP_TEXT && nesc) __hip_atomic_fetch_add(&a.head->escaped, (uint64_t)nesc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+extern __shared__ uint4 responses_window[];
+
+__global__ void __launch_bounds__(64) responses_write_kernel(ResponsesArgs a) {
+  const uint32_t lane = threadIdx.x, i0 = blockIdx.x * kMsgWaveItems, i = i0 + lane;
+  const uint32_t i1 = i0 + kMsgWaveItems < a.n ? i0 + kMsgWaveItems : a.n;
+  const uint64_t rb = a.off[i0], re = a.off[i1];  // the wave's byte range
+  if (re <= rb) return;                           // uniform: 64 empty responses
+  const RspCtx X = responses_ctx(a);
+  RspItem it;
+  it.form = RF_SHORT;
+  it.nparts = 0;
+  it.mask = 0;
+  uint64_t mb = rb, row = 0;
+  uint32_t col = 0, word = 0, len = 0;
+  if (i < a.n) {
+    mb = a.off[i];
+    row = a.drow[i];
+    col = a.col[i];
+    // the length the offsets were scanned from: an item left to the host has none, and nothing is
+    // written past it whatever the parts give
+    len = (uint32_t)(a.off[i + 1] - mb);
+    if (len != a.len[i] || row >= a.cols.c.rows || col >= a.npol || col >= X.S.ncols) len = 0;
+    if (len) {
+      word = a.words[row * a.npol + col];
+      if (rsp_item(X.S, col, word, &it) != RSP_TEXT) len = 0;
+    }
+  }
+  uint8_t* lds = (uint8_t*)responses_window;
+  const uint64_t w0 = rb & ~(uint64_t)15u;
+  uint64_t nwin = 0;
+  for (uint64_t wb = w0; wb < re; wb += a.window, ++nwin) {  // uniform
+    uint32_t skip, at, n;
+    msg_clip(mb, len, wb, a.window, &skip, &at, &n);
+    if (n) rsp_render_window(X, row, col, word, it, skip, n, lds + at);
+    __syncthreads();  // one wave: the LDS writes are done before any lane reads the window
+    const uint64_t lo = wb > rb ? wb : rb, hi = wb + a.window < re ? wb + a.window : re;
+    uint64_t body, tail;
+    msg_chunks(lo, hi, &body, &tail);
+    for (uint64_t g = lo + lane; g < body; g += 64u) a.text[g - a.text_base] = lds[g - wb];
+    for (uint64_t g = body + 16u * lane; g < tail; g += 16u * 64u)
+      *(uint4*)(a.text + (g - a.text_base)) = *(const uint4*)(lds + (g - wb));
+    for (uint64_t g = tail + lane; g < hi; g += 64u) a.text[g - a.text_base] = lds[g - wb];
+    __syncthreads();  // the window is read before the next one is filled
+  }
+  const uint64_t span = __popcll(__ballot(msg_windows_of(mb, len, w0, a.window) > 1u));
+  if (lane == 0u) {
+    __hip_atomic_fetch_add(&a.head->windows, nwin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (span) __hip_atomic_fetch_add(&a.head->spanning, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+hipError_t launch_responses_len(const ResponsesArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(responses_len_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_responses_write(const ResponsesArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  if (a.window < kMsgMinWindow || a.window > kMsgMaxWindow || (a.window & 15u) || (a.text_base & 15u)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(responses_write_kernel, dim3((a.n + kMsgWaveItems - 1u) / kMsgWaveItems), dim3(64), a.window, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace kw

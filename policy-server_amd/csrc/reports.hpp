@@ -10,6 +10,7 @@
 #include "messages.hpp"
 #include "outcomes.hpp"
 #include "packed.hpp"
+#include "responses.hpp"
 #include "summary.hpp"
 
 namespace kw {
@@ -204,5 +205,42 @@ struct MessagesArgs {
 hipError_t launch_messages_len(const MessagesArgs& a, hipStream_t s);
 hipError_t launch_messages_scan(const MessagesArgs& a, hipStream_t s);
 hipError_t launch_messages_write(const MessagesArgs& a, hipStream_t s);
+
+// The AdmissionResponse bodies of chosen pairs (kw_batch_responses; the forms, the parts, the
+// escaping and the table: responses.hpp): the steps of the messages over one round of n items.
+//   len      one lane per item: rsp_item gives the form or leaves the item to the host, rsp_measure
+//            walks the item's parts (the head, the message, two per cause, the tail) and sums their
+//            escaped lengths; the members' words of a group are read from the same row of the
+//            pass. The pieces that grew by escaping are counted into head->escaped.
+//   scan     the messages' scan kernels over these lengths (launch_messages_scan on a MessagesArgs
+//            that names len, off, sums, base and n).
+//   write    messages_write_kernel's walk: a workgroup of one wave owns 64 consecutive items and
+//            their contiguous byte range, in windows of `window` bytes of LDS. A lane whose response
+//            touches the window walks its parts again (rsp_render_window) and writes the bytes
+//            inside it: pieces without escapes by the dword copy, escaped ones byte by byte, an
+//            escape cut by the window's edge in part. The window leaves by aligned 16-byte stores.
+// Plain vector loads and stores and relaxed agent-scope vector atomics (the counters of head) only.
+struct ResponsesHead {
+  uint64_t windows, spanning, escaped;
+  uint32_t missing, pad;
+};
+struct ResponsesArgs {
+  const uint32_t* words;    // [rows][npol], device-row order
+  MsgCols cols;             // the device columns (device rows) and the container names
+  DigestStr uid;            // the uid column, device rows
+  const uint8_t* settings;  // the responses' table (rsp_settings)
+  const uint32_t* drow;     // [n] device rows
+  const uint32_t* col;      // [n]
+  uint32_t* len;            // [n]
+  uint32_t* out_words;      // [n] or nullptr
+  uint8_t* mark;            // [n] 1: left to the host
+  const uint64_t* off;      // [n + 1] (the scan's)
+  uint8_t* text;
+  ResponsesHead* head;
+  uint64_t text_base;
+  uint32_t n, npol, window;
+};
+hipError_t launch_responses_len(const ResponsesArgs& a, hipStream_t s);
+hipError_t launch_responses_write(const ResponsesArgs& a, hipStream_t s);
 
 }  // namespace kw

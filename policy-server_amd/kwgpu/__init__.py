@@ -911,6 +911,38 @@ class Batch:
         raise_for(self._L.kw_debug_messages_stats(self._h, out), "the batch never rendered messages")
         return dict(zip(("rounds", "windows", "spanning", "host", "uploaded_names"), (int(x) for x in out)))
 
+    def responses(self, env, policies, rows, cols, words=False, cap=None, host_cap=None):
+        """The AdmissionResponse bodies of the items (rows[i], cols[i]) of the last all-pairs device
+        pass over `policies` (kw_batch_responses), rendered on the device: Messages(off, text, words,
+        host), item i's JSON text[off[i]:off[i + 1]] (Messages.get(i)), byte for byte what
+        format_response gives with the members' words of the same row; the items in `host` have the
+        empty response here and are left to format_response. `cap` and `host_cap` as for messages()."""
+        arr = env._array(policies)
+        return self._messages_call(lambda r, c, n, st: self._L.kw_batch_responses(self._h, env._h, arr, len(policies), r, c, n, st),
+                                   rows, cols, words, cap, host_cap)
+
+    def responses_from_words(self, env, policies, words, rows, cols, how=0, with_words=False, cap=None, host_cap=None):
+        """Diagnostic (kw_debug_responses_words): the same output on the host from full words
+        [rows][npol] and this batch's host columns. how=0: one format_response per item (the
+        reference); how=1: the part and piece renderer the device runs."""
+        import numpy as np
+        arr = env._array(policies)
+        npol = len(policies)
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        nrows = words.size // npol
+        wp = words.ctypes.data_as(C.POINTER(C.c_uint32))
+        return self._messages_call(
+            lambda r, c, n, st: self._L.kw_debug_responses_words(env._h, self._h, arr, npol, wp, nrows, r, c, n, how, st),
+            rows, cols, with_words, cap, host_cap)
+
+    def debug_responses_stats(self):
+        """Diagnostic (kw_debug_responses_stats): what the last responses() did, as a dict: the rounds,
+        the staging windows written, the responses that spanned a window, the items left to the host,
+        whether the call uploaded a side column, the pieces that grew by escaping."""
+        out = (C.c_uint64 * 6)()
+        raise_for(self._L.kw_debug_responses_stats(self._h, out), "the batch never rendered responses")
+        return dict(zip(("rounds", "windows", "spanning", "host", "uploaded_side", "escaped"), (int(x) for x in out)))
+
     def finding_key(self, row, word):
         """The key bytes of the finding `word` at batch row `row` (kw_batch_finding_key), host only:
         (key, value) for KW_R_LABEL_CONSTRAINT, else (key, None); a numeric or empty key is b""."""

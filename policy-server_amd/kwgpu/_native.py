@@ -133,6 +133,9 @@ class KwMessages(C.Structure):
                 ("nhost", C.c_size_t)]
 
 
+KwResponses = KwMessages  # kw_responses: the fields of kw_messages, same meaning
+
+
 EXPORTS = [
     "kw_env_build", "kw_env_build_yaml", "kw_yaml_to_json", "kw_env_serialize", "kw_env_deserialize", "kw_env_destroy", "kw_env_lookup",
     "kw_env_policy_count", "kw_env_policy_id", "kw_env_is_group", "kw_env_get_policy_mode",
@@ -151,6 +154,7 @@ EXPORTS = [
     "kw_batch_digest", "kw_debug_digest_words", "kw_batch_finding_key", "kw_debug_digest_stats",
     "kw_batch_digest_members", "kw_debug_digest_members_words",
     "kw_batch_messages", "kw_debug_messages_words", "kw_debug_messages_stats",
+    "kw_batch_responses", "kw_debug_responses_words", "kw_debug_responses_stats",
     "kw_metrics_add_outcomes", "kw_metrics_record_pass", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
     "kw_batch_destroy", "kw_debug_host_walk", "kw_validate_batch", "kw_validate_rows", "kw_batch_verdicts",
     "kw_validate_timed", "kw_format_response", "kw_format_response_doc", "kw_env_group_members", "kw_evaluate",
@@ -252,6 +256,10 @@ def lib():
         "kw_debug_messages_words": (ip, [vp, vp, C.POINTER(i32), u32, C.POINTER(u32), u64, C.POINTER(u64), C.POINTER(u32), sz, ip,
                                          C.POINTER(KwMessages)]),
         "kw_debug_messages_stats": (ip, [vp, C.POINTER(u64)]),
+        "kw_batch_responses": (ip, [vp, vp, C.POINTER(i32), u32, C.POINTER(u64), C.POINTER(u32), sz, C.POINTER(KwResponses)]),
+        "kw_debug_responses_words": (ip, [vp, vp, C.POINTER(i32), u32, C.POINTER(u32), u64, C.POINTER(u64), C.POINTER(u32), sz, ip,
+                                          C.POINTER(KwResponses)]),
+        "kw_debug_responses_stats": (ip, [vp, C.POINTER(u64)]),
         "kw_metrics_add_outcomes": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64, C.POINTER(u64), u32, C.POINTER(u64)]),
         "kw_metrics_record_pass": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64]),
         "kw_batch_pin_host": (ip, [vp, ip]),
