@@ -2983,11 +2983,12 @@ bool emit_script(const ExprAst& ast, std::vector<uint8_t>* out, uint32_t* depth,
     walk(ast.root.get());
     for (const FnDef& f : ast.fns) walk(f.body.get());
     std::vector<uint32_t> work(cs.begin(), cs.end());
-    if (cs.count(0x3A3)) work.push_back(0x3C2);
     while (!work.empty()) {
       const uint32_t c = work.back();
       work.pop_back();
       cs.insert(c);
+      // (wherever Σ enters, a literal's or a mapping's: to_lower can turn it into ς)
+      if (c == 0x3A3 && !cs.count(0x3C2)) work.push_back(0x3C2);
       for (const UniCaseMap* m : {uni_map(kUniLower, kUniLowerN, c), uni_map(kUniUpper, kUniUpperN, c)})
         if (m)
           for (uint32_t j = 0; j < m->n; ++j)
