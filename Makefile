@@ -16,7 +16,7 @@ HIPDEF := -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra $(HIPDEF)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -munsafe-fp-atomics $(HIPEXTRA)
 
-HOST_SRCS := json yaml automaton expr env flatten service slotplan metrics knobs pools plan pass upload bulk bulkout packed lastpass summary outcomes digest members messages responses capi
+HOST_SRCS := json yaml automaton expr env flatten service slotplan metrics knobs pools plan pass upload bulk bulkout packed lastpass summary outcomes digest members messages responses patches capi
 HOST_OBJS := $(addprefix $(OBJ)/,$(addsuffix .o,$(HOST_SRCS)))
 # the device objects: the hot path (kernels.hip), the reports over its verdict words (reports.hip)
 # and the wide path's combine kernel with the group programs' VM (groups.hip)

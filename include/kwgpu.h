@@ -770,6 +770,86 @@ int kw_debug_responses_words(const kw_env *env, const kw_batch *b, const int32_t
  * and the pieces whose escaped length exceeded their raw length. KW_E_ARG for a batch that never ran
  * the call. */
 int kw_debug_responses_stats(const kw_batch *b, uint64_t *out);
+
+/* ---- accepted mutations: the JSONPatch of a pair, from columns ------------------------------------
+ * The patch of a psp-capabilities policy needs the container's capability lists (columns already) and
+ * the shape of the document around them. The batch keeps that shape in two host-side columns beside
+ * kw_soa (whose layout is unchanged): per container a u32 KW_PS_PLACE(shape, index), index the item's
+ * place in its own JSON array (containers, initContainers or ephemeralContainers; items that are no
+ * objects count), and per request a u8 KW_PP_* naming the Pod-spec pointer. kw_batch_from_json fills
+ * both; a batch made from a kw_soa holds "unknown" everywhere until kw_batch_set_patch_shape. */
+enum kw_patch_shape {
+  KW_PS_UNKNOWN = 0,
+  KW_PS_NO_SC = 1,    /* securityContext is no object (absent, null, a string, ...) */
+  KW_PS_NO_CAPS = 2,  /* securityContext is an object, capabilities is none */
+  KW_PS_CAPS = 3,     /* capabilities is an object; plus KW_PS_ADD_ARRAY and / or KW_PS_DROP_ARRAY: */
+  KW_PS_ADD_ARRAY = 1,  /*   `add` is an array  */
+  KW_PS_DROP_ARRAY = 2, /*   `drop` is an array */
+  KW_PS_MAX = 6
+};
+#define KW_PS_SHIFT 28
+#define KW_PS_INDEX_MASK 0x0fffffffu
+#define KW_PS_PLACE(shape, index) (((uint32_t)(shape) << KW_PS_SHIFT) | ((uint32_t)(index) & KW_PS_INDEX_MASK))
+#define KW_PS_SHAPE(place) ((uint32_t)(place) >> KW_PS_SHIFT)
+#define KW_PS_INDEX(place) ((uint32_t)(place) & KW_PS_INDEX_MASK)
+enum kw_patch_pointer {
+  KW_PP_UNKNOWN = 0,
+  KW_PP_NONE = 1,      /* the object has no Pod spec: the patch is [] */
+  KW_PP_POD = 2,       /* /spec */
+  KW_PP_TEMPLATE = 3,  /* /spec/template/spec */
+  KW_PP_CRONJOB = 4    /* /spec/jobTemplate/spec/template/spec */
+};
+/* Sets both columns. n_containers and n_requests must be the batch's, every shape <= KW_PS_MAX and
+ * every pointer <= KW_PP_CRONJOB, else KW_E_ARG and the batch is unchanged. Before or after
+ * kw_batch_to_device: a device copy of the columns is dropped and uploaded again on next use. */
+int kw_batch_set_patch_shape(kw_batch *b, const uint32_t *ctr_place, uint64_t n_containers,
+                             const uint8_t *req_place, uint64_t n_requests);
+/* Reads both columns back (either pointer may be NULL); the sizes must be the batch's. */
+int kw_batch_patch_shape(const kw_batch *b, uint32_t *ctr_place, uint64_t n_containers, uint8_t *req_place,
+                         uint64_t n_requests);
+enum kw_patch_form {
+  KW_PATCH_OPS = 0,      /* the RFC 6902 ops: [{"op":"add","path":...,"value":...},...] */
+  KW_PATCH_RESPONSE = 1  /* {"uid":U,"allowed":true,"patchType":"JSONPatch","patch":"<base64 of the ops>"} */
+};
+/* One pair's patch from the host columns, without the document: byte for byte the ops
+ * capabilities_patch cuts from the document (form KW_PATCH_OPS), or the response
+ * kw_format_response_doc writes (KW_PATCH_RESPONSE). buf / cap / need as kw_format_response. KW_E_ARG,
+ * with a message in buf that names what is missing, where kw_batch_patches lists the item for the
+ * host: a verdict without KW_F_PATCH, a policy that is no psp-capabilities policy (where
+ * kw_format_response_doc answers KW_E_ENGINE), a request whose pointer or a container whose shape is
+ * unknown. */
+int kw_format_patch(const kw_env *env, const kw_batch *b, uint64_t row, int32_t policy, uint32_t verdict, int form,
+                    char *buf, size_t cap, size_t *need);
+/* The patches of chosen pairs of the last all-pairs device pass, rendered on the device: item i is
+ * what kw_format_patch(env, b, rows[i], policies[cols[i]], w, form, ...) writes, w the pass's word at
+ * the pair. The fields, the capacities, KW_E_NOSPACE (bytes, nhost and all of off exact), the
+ * argument errors (a rows-mode pass, a policy list of another length, a row or a column outside the
+ * pass: KW_E_ARG), any order and repeats of items, batch rows for a split batch, page-locked or
+ * pageable `text`, the same bytes for the same input and "leaves the batch good for further calls"
+ * are word for word kw_batch_responses' contract. The items in `host` have a zero length here:
+ *   an item whose word has no KW_F_PATCH; an item whose column is no psp-capabilities policy; an item
+ *   whose request's pointer is KW_PP_UNKNOWN; an item one of whose containers has shape
+ *   KW_PS_UNKNOWN; an item whose row or container range the columns do not hold.
+ * So the host list of kw_batch_responses can be handed to this call as it stands: its KW_F_PATCH
+ * items are rendered, the others listed again. The two shape columns, like the uid column, are
+ * uploaded from the host batch by the first call (in device-row order for a split batch) and kept
+ * until the batch is uploaded again, the shape is set again or the batch is destroyed. A capability
+ * column that the pass did not make resident is KW_E_ARG. Rounds of KW_MESSAGES_CHUNK, windows of
+ * KW_MESSAGES_WINDOW bytes. Synchronises with the pass's stream. */
+int kw_batch_patches(kw_batch *b, const kw_env *env, const int32_t *policies, uint32_t npol,
+                     const uint64_t *rows, const uint32_t *cols, size_t n, int form, kw_responses *out);
+/* Diagnostic (tests, documents): the same output on the host from full words [nrows][npol] and the
+ * host batch. how = 0: one kw_format_patch per item, the reference (an item it answers an error for
+ * is listed in host); how = 1: the renderer the device runs (csrc/patches.hpp), in the device's
+ * rounds and windows, over the host columns. */
+int kw_debug_patches_words(const kw_env *env, const kw_batch *b, const int32_t *policies, uint32_t npol,
+                           const uint32_t *words, uint64_t nrows, const uint64_t *rows, const uint32_t *cols,
+                           size_t n, int form, int how, kw_responses *out);
+/* Diagnostic (tests): what the batch's last kw_batch_patches did. out[0..5): the rounds, the staging
+ * windows written, the items that spanned more than one window, the items listed for the host,
+ * whether that call uploaded a side column (the shapes or the uids; 1 / 0). KW_E_ARG for a batch that
+ * never ran the call. */
+int kw_debug_patches_stats(const kw_batch *b, uint64_t *out);
 /* Page-lock the batch's large host column arrays in place (hipHostRegister; undone by
  * kw_batch_destroy) so kw_validate_host sends them to the device by DMA from where they lie instead
  * of through the pinned staging its host workers fill. For a caller that runs several bulk passes

@@ -145,6 +145,12 @@ struct Batch {
   std::vector<uint8_t> ctr_flags;
   std::vector<uint32_t> capadd_off{0}, capdrop_off{0};
   StrCol ctr_name, ctr_image, ctr_aa, cap_add, cap_drop, lbl_key, lbl_val;
+  // The shape a JSONPatch is cut to (include/kwgpu.h KW_PS_*, KW_PP_*; patches.hpp), host only and
+  // not part of kw_soa: per container its shape code and its index in its own JSON array, per
+  // request the Pod-spec pointer. The flattener fills them; a batch made from a kw_soa holds
+  // "unknown" until kw_batch_set_patch_shape.
+  std::vector<uint32_t> ctr_place;
+  std::vector<uint8_t> req_place;
   DeviceBatch* dev = nullptr;
   WideData wide;  // side data of the last pass (kw_batch_verdicts)
   uint64_t containers() const { return ctr_flags.size(); }

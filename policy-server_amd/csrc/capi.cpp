@@ -853,6 +853,43 @@ int kw_debug_responses_words(const kw_env* env, const kw_batch* b, const int32_t
 
 int kw_debug_responses_stats(const kw_batch* b, uint64_t* out) { return debug_responses_stats(b, out); }
 
+int kw_batch_set_patch_shape(kw_batch* b, const uint32_t* ctr_place, uint64_t n_containers, const uint8_t* req_place,
+                             uint64_t n_requests) {
+  return batch_set_patch_shape(b, ctr_place, n_containers, req_place, n_requests);
+}
+
+int kw_batch_patch_shape(const kw_batch* b, uint32_t* ctr_place, uint64_t n_containers, uint8_t* req_place, uint64_t n_requests) {
+  return batch_patch_shape(b, ctr_place, n_containers, req_place, n_requests);
+}
+
+int kw_format_patch(const kw_env* env, const kw_batch* b, uint64_t row, int32_t policy, uint32_t verdict, int form, char* buf,
+                    size_t cap, size_t* need) {
+  if (!env || !b || row >= b->b.n || policy < 0 || (size_t)policy >= env->e.nvisible || (form != KW_PATCH_OPS && form != KW_PATCH_RESPONSE))
+    return KW_E_ARG;
+  std::string out;
+  Status st = format_patch(env->e, b->b, row, policy, verdict, form, &out);
+  if (!st.ok()) {
+    put_out(st.message, buf, cap, need);
+    return st.code;
+  }
+  return put_out(out, buf, cap, need);
+}
+
+int kw_batch_patches(kw_batch* b, const kw_env* env, const int32_t* policies, uint32_t npol, const uint64_t* rows,
+                     const uint32_t* cols, size_t n, int form, kw_responses* out) {
+  if (!b || !env || !out || (npol && !policies)) return KW_E_ARG;
+  return batch_patches(b, env, policies, npol, rows, cols, n, form, out);
+}
+
+int kw_debug_patches_words(const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol, const uint32_t* words,
+                           uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int form, int how,
+                           kw_responses* out) {
+  if (!b || !env || !out || (npol && !policies)) return KW_E_ARG;
+  return debug_patches_words(env, b, policies, npol, words, nrows, rows, cols, n, form, how, out);
+}
+
+int kw_debug_patches_stats(const kw_batch* b, uint64_t* out) { return debug_patches_stats(b, out); }
+
 int kw_validate_timed(const kw_env* env, kw_batch* b, const int32_t* policies, uint32_t npol, int origin, int warmup,
                       int reps, kw_timing* out) {
   return validate_timed(env, b, policies, npol, origin, warmup, reps, out);

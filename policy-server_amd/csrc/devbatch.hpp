@@ -231,6 +231,17 @@ struct DeviceBatch {
   // escaping
   bool responses_ran = false;
   uint64_t responses_stats[6] = {0, 0, 0, 0, 0, 0};
+  // the patch-shape columns (kw_batch_patches uploads them on first use, as the uids are; dropped
+  // by kw_batch_set_patch_shape), in the device's container and row order: one block
+  // [u32 per container | u8 per row]
+  uint8_t* places = nullptr;
+  size_t places_bytes = 0;
+  const uint32_t* ctr_place = nullptr;
+  const uint8_t* req_place = nullptr;
+  // the last kw_batch_patches (kw_debug_patches_stats): rounds, windows written, items that spanned
+  // a window, items left to the host, whether it uploaded a side column (the last is unused)
+  bool patches_ran = false;
+  uint64_t patches_stats[6] = {0, 0, 0, 0, 0, 0};
   // tile capacities of this batch (plan_pass), per tile height tried
   struct RowsPlan {
     uint32_t rows = 0;
@@ -257,6 +268,7 @@ struct DeviceBatch {
     P.release(device, cols, cols_bytes);
     P.release(device, names, names_bytes);
     P.release(device, uids, uids_bytes);
+    P.release(device, places, places_bytes);
     P.release(device, verdicts, verdict_cap * 4);
     P.release(device, g_cls, g_cls_cap * 2);
     P.release(device, nfa_cls, nfa_cls_cap * 2);

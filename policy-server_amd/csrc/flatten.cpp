@@ -53,6 +53,8 @@ void Batch::append(const Batch& o) {
   ctr_flags.insert(ctr_flags.end(), o.ctr_flags.begin(), o.ctr_flags.end());
   shift(&capadd_off, o.capadd_off);
   shift(&capdrop_off, o.capdrop_off);
+  ctr_place.insert(ctr_place.end(), o.ctr_place.begin(), o.ctr_place.end());
+  req_place.insert(req_place.end(), o.req_place.begin(), o.req_place.end());
   StrCol* mine[] = {&uid, &ns, &op, &kind, &rkind, &ctr_name, &ctr_image, &ctr_aa, &cap_add, &cap_drop, &lbl_key, &lbl_val};
   const StrCol* theirs[] = {&o.uid, &o.ns, &o.op, &o.kind, &o.rkind, &o.ctr_name, &o.ctr_image, &o.ctr_aa,
                             &o.cap_add, &o.cap_drop, &o.lbl_key, &o.lbl_val};
@@ -139,6 +141,11 @@ void flatten_request(const JDoc& d, int64_t req, const int64_t* rk, bool raw, Ba
   const int64_t spec = ps.spec, tmpl_meta = ps.meta;
   if (spec >= 0) rf |= KW_REQ_HAS_PODSPEC;
   b->req_flags.push_back(rf);
+  // the pointer capabilities_patch (service.cpp) prefixes its paths with: find_podspec's, which
+  // follows object.kind before request.kind.kind
+  uint8_t pp = KW_PP_NONE;
+  if (spec >= 0) pp = ps.pointer[5] == '\0' ? KW_PP_POD : ps.pointer[6] == 't' ? KW_PP_TEMPLATE : KW_PP_CRONJOB;
+  b->req_place.push_back(pp);
 
   // containers
   if (spec >= 0) {
@@ -154,7 +161,9 @@ void flatten_request(const JDoc& d, int64_t req, const int64_t* rk, bool raw, Ba
     for (int li = 0; li < 3; ++li) {
       const int64_t arr = arrs[li];
       if (arr < 0 || !d.is((uint32_t)arr, JType::Arr)) continue;
+      uint32_t item = 0;  // the index in the JSON array: the items skipped below count
       for (uint32_t c : d.members((uint32_t)arr)) {
+        const uint32_t ki = item++;
         if (!d.is(c, JType::Obj)) continue;
         uint8_t cf = kinds[li];
         int64_t f[3], sc[2] = {-1, -1}, caps[2] = {-1, -1};
@@ -168,6 +177,16 @@ void flatten_request(const JDoc& d, int64_t req, const int64_t* rk, bool raw, Ba
         if (sc[1] >= 0) d.pick((uint32_t)sc[1], kCaps, 2, caps);
         push_caps(d, caps[0], &b->cap_add, &b->capadd_off);
         push_caps(d, caps[1], &b->cap_drop, &b->capdrop_off);
+        // the shape as capabilities_patch's sc_obj, caps_obj, add_arr and drop_arr decide it (the
+        // same members: pick and get both keep the last of a repeated key)
+        uint32_t shape = KW_PS_NO_SC;
+        if (f[2] >= 0 && d.is((uint32_t)f[2], JType::Obj)) {
+          shape = KW_PS_NO_CAPS;
+          if (sc[1] >= 0 && d.is((uint32_t)sc[1], JType::Obj))
+            shape = (uint32_t)KW_PS_CAPS + (caps[0] >= 0 && d.is((uint32_t)caps[0], JType::Arr) ? (uint32_t)KW_PS_ADD_ARRAY : 0u) +
+                    (caps[1] >= 0 && d.is((uint32_t)caps[1], JType::Arr) ? (uint32_t)KW_PS_DROP_ARRAY : 0u);
+        }
+        b->ctr_place.push_back(KW_PS_PLACE(shape, ki));
         std::string_view profile;
         if (have_annots) {
           for (uint32_t kid : d.members((uint32_t)annots)) {
@@ -349,6 +368,8 @@ bool batch_from_soa(const kw_soa& s, Batch* b, std::string* err) {
   b->ctr_flags.assign(s.ctr_flags + s.ctr_off[0], s.ctr_flags + s.ctr_off[n]);
   b->capadd_off.assign(s.capadd_off, s.capadd_off + nc + 1);
   b->capdrop_off.assign(s.capdrop_off, s.capdrop_off + nc + 1);
+  b->ctr_place.assign(nc, KW_PS_PLACE(KW_PS_UNKNOWN, 0));  // not part of kw_soa (kw_batch_set_patch_shape)
+  b->req_place.assign(n, (uint8_t)KW_PP_UNKNOWN);
   if (s.ctr_off[0] != 0 || s.lbl_off[0] != 0 || s.capadd_off[0] != 0 || s.capdrop_off[0] != 0) {
     *err = "SoA offsets must start at 0";
     return false;

@@ -140,4 +140,15 @@ int debug_responses_words(const kw_env* env, const kw_batch* b, const int32_t* p
                           uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int how, kw_responses* out);
 int debug_responses_stats(const kw_batch* b, uint64_t* out);
 
+// The JSONPatch of accepted mutations from columns (patches.cpp): the patch-shape columns,
+// kw_batch_patches over the last all-pairs pass, and the host renderers and the statistics of the
+// diagnostics.
+int batch_set_patch_shape(kw_batch* b, const uint32_t* ctr_place, uint64_t n_containers, const uint8_t* req_place, uint64_t n_requests);
+int batch_patch_shape(const kw_batch* b, uint32_t* ctr_place, uint64_t n_containers, uint8_t* req_place, uint64_t n_requests);
+int batch_patches(kw_batch* b, const kw_env* env, const int32_t* policies, uint32_t npol, const uint64_t* rows, const uint32_t* cols,
+                  size_t n, int form, kw_responses* out);
+int debug_patches_words(const kw_env* env, const kw_batch* b, const int32_t* policies, uint32_t npol, const uint32_t* words,
+                        uint64_t nrows, const uint64_t* rows, const uint32_t* cols, size_t n, int form, int how, kw_responses* out);
+int debug_patches_stats(const kw_batch* b, uint64_t* out);
+
 }  // namespace kw

@@ -798,6 +798,27 @@ __global__ void __launch_bounds__(kMsgScanThreads) messages_scan_kernel(Messages
 
 extern __shared__ uint4 messages_window[];
 
+// What the write kernels of the messages, the responses and the patches share: the window [wb, wb +
+// window) of LDS, filled by the lanes, leaves for the wave's byte range [rb, re) of the text: aligned
+// 16-byte stores, the range's unaligned head and tail in single bytes, nothing outside the range.
+__device__ inline void window_store(uint8_t* text, uint64_t text_base, const uint8_t* lds, uint64_t wb, uint32_t window, uint64_t rb,
+                                    uint64_t re, uint32_t lane) {
+  __syncthreads();  // one wave: the LDS writes are done before any lane reads the window
+  const uint64_t lo = wb > rb ? wb : rb, hi = wb + window < re ? wb + window : re;
+  uint64_t body, tail;
+  msg_chunks(lo, hi, &body, &tail);
+  for (uint64_t g = lo + lane; g < body; g += 64u) text[g - text_base] = lds[g - wb];
+  for (uint64_t g = body + 16u * lane; g < tail; g += 16u * 64u) *(uint4*)(text + (g - text_base)) = *(const uint4*)(lds + (g - wb));
+  for (uint64_t g = tail + lane; g < hi; g += 64u) text[g - text_base] = lds[g - wb];
+  __syncthreads();  // the window is read before the next one is filled
+}
+// One lane adds the wave's windows and its items that spanned more than one to the call's counters.
+template <typename Head>
+__device__ inline void window_counts(Head* head, uint64_t nwin, uint64_t span) {
+  __hip_atomic_fetch_add(&head->windows, nwin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (span) __hip_atomic_fetch_add(&head->spanning, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __global__ void __launch_bounds__(64) messages_write_kernel(MessagesArgs a) {
   const uint32_t lane = threadIdx.x, i0 = blockIdx.x * kMsgWaveItems, i = i0 + lane;
   const uint32_t i1 = i0 + kMsgWaveItems < a.n ? i0 + kMsgWaveItems : a.n;
@@ -828,21 +849,10 @@ __global__ void __launch_bounds__(64) messages_write_kernel(MessagesArgs a) {
     uint32_t skip, at, n;
     msg_clip(mb, P.len, wb, a.window, &skip, &at, &n);
     if (n) msg_copy_window(P, skip, n, lds + at);
-    __syncthreads();  // one wave: the LDS writes are done before any lane reads the window
-    const uint64_t lo = wb > rb ? wb : rb, hi = wb + a.window < re ? wb + a.window : re;
-    uint64_t body, tail;
-    msg_chunks(lo, hi, &body, &tail);
-    for (uint64_t g = lo + lane; g < body; g += 64u) a.text[g - a.text_base] = lds[g - wb];
-    for (uint64_t g = body + 16u * lane; g < tail; g += 16u * 64u)
-      *(uint4*)(a.text + (g - a.text_base)) = *(const uint4*)(lds + (g - wb));
-    for (uint64_t g = tail + lane; g < hi; g += 64u) a.text[g - a.text_base] = lds[g - wb];
-    __syncthreads();  // the window is read before the next one is filled
+    window_store(a.text, a.text_base, lds, wb, a.window, rb, re, lane);
   }
   const uint64_t span = __popcll(__ballot(msg_windows_of(mb, P.len, w0, a.window) > 1u));
-  if (lane == 0u) {
-    __hip_atomic_fetch_add(&a.head->windows, nwin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (span) __hip_atomic_fetch_add(&a.head->spanning, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (lane == 0u) window_counts(a.head, nwin, span);
 }
 
 hipError_t launch_messages_len(const MessagesArgs& a, hipStream_t s) {
@@ -933,21 +943,10 @@ __global__ void __launch_bounds__(64) responses_write_kernel(ResponsesArgs a) {
     uint32_t skip, at, n;
     msg_clip(mb, len, wb, a.window, &skip, &at, &n);
     if (n) rsp_render_window(X, row, col, word, it, skip, n, lds + at);
-    __syncthreads();  // one wave: the LDS writes are done before any lane reads the window
-    const uint64_t lo = wb > rb ? wb : rb, hi = wb + a.window < re ? wb + a.window : re;
-    uint64_t body, tail;
-    msg_chunks(lo, hi, &body, &tail);
-    for (uint64_t g = lo + lane; g < body; g += 64u) a.text[g - a.text_base] = lds[g - wb];
-    for (uint64_t g = body + 16u * lane; g < tail; g += 16u * 64u)
-      *(uint4*)(a.text + (g - a.text_base)) = *(const uint4*)(lds + (g - wb));
-    for (uint64_t g = tail + lane; g < hi; g += 64u) a.text[g - a.text_base] = lds[g - wb];
-    __syncthreads();  // the window is read before the next one is filled
+    window_store(a.text, a.text_base, lds, wb, a.window, rb, re, lane);
   }
   const uint64_t span = __popcll(__ballot(msg_windows_of(mb, len, w0, a.window) > 1u));
-  if (lane == 0u) {
-    __hip_atomic_fetch_add(&a.head->windows, nwin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (span) __hip_atomic_fetch_add(&a.head->spanning, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (lane == 0u) window_counts(a.head, nwin, span);
 }
 
 hipError_t launch_responses_len(const ResponsesArgs& a, hipStream_t s) {
@@ -960,6 +959,100 @@ hipError_t launch_responses_write(const ResponsesArgs& a, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   if (a.window < kMsgMinWindow || a.window > kMsgMaxWindow || (a.window & 15u) || (a.text_base & 15u)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(responses_write_kernel, dim3((a.n + kMsgWaveItems - 1u) / kMsgWaveItems), dim3(64), a.window, s, a);
+  return hipGetLastError();
+}
+
+// ---- the JSONPatch of accepted mutations (reports.hpp PatchesArgs, patches.hpp) ------------------------
+
+__device__ inline PatchCtx patches_ctx(const PatchesArgs& pa) {
+  PatchCtx X;
+  X.C = pa.c;
+  X.S = patch_settings(pa.r.settings);
+  return X;
+}
+
+__global__ void __launch_bounds__(256) patches_len_kernel(PatchesArgs pa) {
+  const ResponsesArgs& a = pa.r;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  const uint64_t row = a.drow[i];
+  const uint32_t col = a.col[i];
+  uint32_t word = 0, st = PATCH_HOST, len = 0;
+  if (row < pa.c.rows && col < a.npol) {  // (the host checked both: nothing is read outside the pass)
+    const PatchCtx X = patches_ctx(pa);
+    word = a.words[row * a.npol + col];
+    if (col < X.S.ncols) st = patch_length(X, row, col, word, pa.form, &len);
+  }
+  a.len[i] = st == PATCH_TEXT ? len : 0u;
+  a.mark[i] = st == PATCH_HOST ? 1u : 0u;
+  if (a.out_words) a.out_words[i] = word;
+  if (st == PATCH_MISSING) __hip_atomic_store(&a.head->missing, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+extern __shared__ uint4 patches_window[];
+
+__global__ void __launch_bounds__(64) patches_write_kernel(PatchesArgs pa) {
+  const ResponsesArgs& a = pa.r;
+  const uint32_t lane = threadIdx.x, i0 = blockIdx.x * kMsgWaveItems, i = i0 + lane;
+  const uint32_t i1 = i0 + kMsgWaveItems < a.n ? i0 + kMsgWaveItems : a.n;
+  const uint64_t rb = a.off[i0], re = a.off[i1];  // the wave's byte range
+  if (re <= rb) return;                           // uniform: 64 items without text
+  const PatchCtx X = patches_ctx(pa);
+  const bool response = pa.form == (uint32_t)KW_PATCH_RESPONSE;
+  PatchEnvelope env;
+  env.uid = nullptr;
+  env.un = env.ue = env.head = 0;
+  uint64_t mb = rb, row = 0;
+  uint32_t col = 0, len = 0, ops = 0;
+  if (i < a.n) {
+    mb = a.off[i];
+    row = a.drow[i];
+    col = a.col[i];
+    // the length the offsets were scanned from: an item left to the host has none, and nothing is
+    // written past it whatever the walk gives
+    len = (uint32_t)(a.off[i + 1] - mb);
+    if (len != a.len[i] || row >= pa.c.rows || col >= a.npol || col >= X.S.ncols) len = 0;
+    if (len && patch_item(X, row, col, a.words[row * a.npol + col], pa.form) != PATCH_TEXT) len = 0;
+    if (len) {
+      ops = patch_measure(X, row, col);
+      if (response) env = patch_envelope(X, row);
+      if ((response ? patch_response_len(env, ops) : ops) != len) len = 0;
+    }
+  }
+  uint8_t* lds = (uint8_t*)patches_window;
+  uint8_t* raw = lds + a.window;  // the raw ops bytes under a lane's base64 quads (patches_raw_bytes)
+  const uint64_t w0 = rb & ~(uint64_t)15u;
+  uint64_t nwin = 0;
+  for (uint64_t wb = w0; wb < re; wb += a.window, ++nwin) {  // uniform
+    uint32_t skip, at, n;
+    msg_clip(mb, len, wb, a.window, &skip, &at, &n);
+    if (n) {
+      // lane k's part of the window starts after lane k - 1's: 3 x (at / 4) + 8 x lane leaves every
+      // lane patch_raw_need(n) bytes of its own
+      if (response) patch_response_window(X, row, col, env, ops, skip, n, lds + at, raw + 3u * (at / 4u) + 8u * lane);
+      else patch_render_window(X, row, col, skip, n, lds + at);
+    }
+    window_store(a.text, a.text_base, lds, wb, a.window, rb, re, lane);
+  }
+  const uint64_t span = __popcll(__ballot(msg_windows_of(mb, len, w0, a.window) > 1u));
+  if (lane == 0u) window_counts(a.head, nwin, span);
+}
+
+// The LDS of the write kernel: the window and the raw bytes beside it.
+static uint32_t patches_raw_bytes(uint32_t window) { return (3u * (window / 4u) + 8u * 64u + 16u + 15u) & ~15u; }
+
+hipError_t launch_patches_len(const PatchesArgs& pa, hipStream_t s) {
+  if (pa.r.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(patches_len_kernel, dim3((pa.r.n + 255u) / 256u), dim3(256), 0, s, pa);
+  return hipGetLastError();
+}
+
+hipError_t launch_patches_write(const PatchesArgs& pa, hipStream_t s) {
+  const ResponsesArgs& a = pa.r;
+  if (a.n == 0) return hipSuccess;
+  if (a.window < kMsgMinWindow || a.window > kMsgMaxWindow || (a.window & 15u) || (a.text_base & 15u)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(patches_write_kernel, dim3((a.n + kMsgWaveItems - 1u) / kMsgWaveItems), dim3(64),
+                     a.window + patches_raw_bytes(a.window), s, pa);
   return hipGetLastError();
 }
 

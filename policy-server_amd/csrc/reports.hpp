@@ -10,6 +10,7 @@
 #include "messages.hpp"
 #include "outcomes.hpp"
 #include "packed.hpp"
+#include "patches.hpp"
 #include "responses.hpp"
 #include "summary.hpp"
 
@@ -242,5 +243,28 @@ struct ResponsesArgs {
 };
 hipError_t launch_responses_len(const ResponsesArgs& a, hipStream_t s);
 hipError_t launch_responses_write(const ResponsesArgs& a, hipStream_t s);
+
+// The JSONPatch of accepted mutations (kw_batch_patches; the walk, the table and the base64 layer:
+// patches.hpp): the frame of the responses (`r`: the items, the lengths, the scan's offsets, the
+// text, the head; its cols and uid are not read), the columns a patch is cut from and the form.
+//   len      one lane per item: patch_item leaves the item to the host or not, patch_measure walks
+//            the row's containers and gives the length of the ops text, the response form adds the
+//            envelope and turns the ops' length into its base64's.
+//   scan     the messages' scan kernels, as for the responses.
+//   write    the responses' walk over windows of LDS (window_store). In the ops form a lane walks
+//            its item again and keeps the bytes inside the window. In the response form the
+//            window's base64 characters need the raw bytes under their quads: the lane renders
+//            those into a second LDS region (3/4 of the window and 8 bytes a lane, each lane a
+//            place of its own) and encodes from there; its span is cut to whole quads counted from
+//            the start of the item's base64 text, so a quad that straddles two windows is encoded
+//            from the same three bytes both times.
+// Plain vector loads and stores and relaxed agent-scope vector atomics (the counters of head) only.
+struct PatchesArgs {
+  ResponsesArgs r;
+  PatchCols c;    // device rows
+  uint32_t form;  // KW_PATCH_OPS / KW_PATCH_RESPONSE
+};
+hipError_t launch_patches_len(const PatchesArgs& a, hipStream_t s);
+hipError_t launch_patches_write(const PatchesArgs& a, hipStream_t s);
 
 }  // namespace kw

@@ -3,8 +3,9 @@
 // the container names on first use, and runs the items in the rounds of the messages: the lengths,
 // their scan (the messages' scan kernels) and the text are three steps a round, the offsets, the
 // words and the host marks come back through a pooled block, the text by direct DMA into page-locked
-// memory or through a bounce block. The two host renderers of the diagnostic. The arithmetic is
-// responses.hpp's, the kernels reports.hip's.
+// memory or through a bounce block (response_rounds, rounds.hpp: kw_batch_patches runs its items
+// through the same rounds with its own two launches). The two host renderers of the diagnostic. The
+// arithmetic is responses.hpp's, the kernels reports.hip's.
 #include "responses.hpp"
 
 #include <chrono>
@@ -16,6 +17,7 @@
 #include "knobs.hpp"
 #include "lastpass.hpp"
 #include "reports.hpp"
+#include "rounds.hpp"
 #include "service.hpp"
 #include "upload.hpp"
 
@@ -58,7 +60,9 @@ int responses_table(const Env& E, const int32_t* policies, uint32_t npol, std::v
   return KW_OK;
 }
 
-bool out_ok(const kw_responses* out, const uint64_t* rows, const uint32_t* cols, size_t n) {
+}  // namespace
+
+bool responses_out_ok(const kw_responses* out, const uint64_t* rows, const uint32_t* cols, size_t n) {
   if (!out) return false;
   if (n && (!rows || !cols || !out->off)) return false;
   return !(out->cap && !out->text) && !(out->host_cap && !out->host);
@@ -106,8 +110,6 @@ int upload_uids(kw_batch* kb, hipStream_t s) {
   return KW_OK;
 }
 
-}  // namespace
-
 int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uint32_t npol, const uint64_t* rows,
                     const uint32_t* cols, size_t n, kw_responses* out) {
   if (!out) return KW_E_ARG;
@@ -116,7 +118,7 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
   if (!env || !F.ok() || npol != F.npol) return KW_E_ARG;
   const uint64_t nrows = F.rows;
   DeviceBatch& D = *F.dev;
-  if (!out_ok(out, rows, cols, n)) return KW_E_ARG;
+  if (!responses_out_ok(out, rows, cols, n)) return KW_E_ARG;
   for (size_t i = 0; i < n; ++i)
     if (rows[i] >= nrows || cols[i] >= npol) return KW_E_ARG;
   std::vector<uint64_t> table;
@@ -127,11 +129,8 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
     if (out->off) out->off[0] = 0;
     return KW_OK;
   }
-  const bool dbg = Knobs::on<KW_BULK_DEBUG>();
-  const auto t_start = std::chrono::steady_clock::now();
-  const size_t chunk = (size_t)Knobs::num<KW_MESSAGES_CHUNK>(), m_max = std::min(chunk, n);
-  const uint32_t window = msg_window_bytes(Knobs::num<KW_MESSAGES_WINDOW>());
-
+  RoundsCall call;
+  call.t_start = std::chrono::steady_clock::now();
   if (int rc = F.open()) return rc;
   hipStream_t s = F.s;
   if (!D.names) {
@@ -142,7 +141,27 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
     if (int rc = upload_uids(b, s)) return rc;
     D.responses_stats[4] = 1;
   }
-  const double side_ms = ms_since(t_start);
+  call.side_ms = ms_since(call.t_start);
+  ResponsesArgs a{};
+  a.cols.c = device_cols(b);
+  a.cols.name = DigestStr{D.name_col.off, D.name_col.bytes, D.name_col.n};
+  a.uid = DigestStr{D.uid_col.off, D.uid_col.bytes, D.uid_col.n};
+  call.len = launch_responses_len;
+  call.write = launch_responses_write;
+  call.what = "responses";
+  call.stats = D.responses_stats;
+  return response_rounds(F, table, a, rows, cols, n, out, call);
+}
+
+int response_rounds(LastPass& F, const std::vector<uint64_t>& table, ResponsesArgs a, const uint64_t* rows, const uint32_t* cols,
+                    size_t n, kw_responses* out, const RoundsCall& call) {
+  DeviceBatch& D = *F.dev;
+  hipStream_t s = F.s;
+  const bool dbg = Knobs::on<KW_BULK_DEBUG>();
+  const auto t_start = call.t_start;
+  const double side_ms = call.side_ms;
+  const size_t chunk = (size_t)Knobs::num<KW_MESSAGES_CHUNK>(), m_max = std::min(chunk, n);
+  const uint32_t window = msg_window_bytes(Knobs::num<KW_MESSAGES_WINDOW>());
   if (D.split) D.device_rows();
 
   // in: [device rows][cols][table]; out: [off][words][marks][head]; the device's lengths and the scan's tile sums beside them
@@ -162,11 +181,7 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
   HIPCHK(hipMemcpyAsync(di + 2 * b_idx, hi + 2 * b_idx, b_set, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(dov + b_off + b_words + b_mark, 0, sizeof(ResponsesHead), s));
 
-  ResponsesArgs a{};
   a.words = D.verdicts;
-  a.cols.c = device_cols(b);
-  a.cols.name = DigestStr{D.name_col.off, D.name_col.bytes, D.name_col.n};
-  a.uid = DigestStr{D.uid_col.off, D.uid_col.bytes, D.uid_col.n};
   a.settings = di + 2 * b_idx;
   a.drow = (const uint32_t*)di;
   a.col = (const uint32_t*)(di + b_idx);
@@ -175,7 +190,7 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
   a.mark = dov + b_off + b_words;
   a.off = (const uint64_t*)dov;
   a.head = (ResponsesHead*)(dov + b_off + b_words + b_mark);
-  a.npol = npol;
+  a.npol = F.npol;
   a.window = window;
   MessagesArgs sc{};  // what the messages' scan kernels read of their arguments
   sc.len = a.len;
@@ -200,7 +215,7 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
     a.n = sc.n = (uint32_t)m;
     sc.base = total;
     t_len.start(s);
-    HIPCHK(launch_responses_len(a, s));
+    HIPCHK(call.len(a, s));
     t_len.stop(s);
     t_scan.start(s);
     HIPCHK(launch_messages_scan(sc, s));
@@ -243,7 +258,7 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
       HIPCHK(dtext.alloc(dev_pool(), D.device, b_text));
       a.text = (uint8_t*)dtext.p;
       t_write.start(s);
-      HIPCHK(launch_responses_write(a, s));
+      HIPCHK(call.write(a, s));
       t_write.stop(s);
       const uint8_t* src = a.text + (total - a.text_base);
       const size_t bytes = (size_t)(end - total);
@@ -265,17 +280,17 @@ int batch_responses(kw_batch* b, const kw_env* env, const int32_t* policies, uin
   HIPCHK(hipMemcpyAsync(ho, a.head, sizeof(ResponsesHead), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   const ResponsesHead head = *(const ResponsesHead*)ho;
-  D.responses_stats[0] = rounds;
-  D.responses_stats[1] = head.windows;
-  D.responses_stats[2] = head.spanning;
-  D.responses_stats[3] = nhost;
-  D.responses_stats[5] = head.escaped;
+  call.stats[0] = rounds;
+  call.stats[1] = head.windows;
+  call.stats[2] = head.spanning;
+  call.stats[3] = nhost;
+  call.stats[5] = head.escaped;
   const bool fits = total <= out->cap && nhost <= out->host_cap;
   if (dbg)
-    fprintf(stderr, "[kw responses] %zu items, %llu bytes, %llu for the host, %llu rounds, window %u%s: side columns %.3f ms, len %.3f ms "
+    fprintf(stderr, "[kw %s] %zu items, %llu bytes, %llu for the host, %llu rounds, window %u%s: side columns %.3f ms, len %.3f ms "
             "scan %.3f ms write %.3f ms on the device (by events), offsets read-back %.3f ms (by events), text read-back %.3f ms (%s), "
             "the call %.3f ms\n",
-            n, (unsigned long long)total, (unsigned long long)nhost, (unsigned long long)rounds, window, fits ? "" : " (more than cap)",
+            call.what, n, (unsigned long long)total, (unsigned long long)nhost, (unsigned long long)rounds, window, fits ? "" : " (more than cap)",
             side_ms, len_ms, scan_ms, write_ms, back_ms, text_ms, direct ? "direct" : "bounce", ms_since(t_start));
   return fits ? KW_OK : KW_E_NOSPACE;
 }
@@ -287,7 +302,7 @@ int debug_responses_words(const kw_env* env, const kw_batch* b, const int32_t* p
   if (!out) return KW_E_ARG;
   out->bytes = out->nhost = 0;
   if (!env || !b || npol == 0 || nrows > b->b.n || (nrows && !words) || (how != 0 && how != 1)) return KW_E_ARG;
-  if (!out_ok(out, rows, cols, n)) return KW_E_ARG;
+  if (!responses_out_ok(out, rows, cols, n)) return KW_E_ARG;
   for (size_t i = 0; i < n; ++i)
     if (rows[i] >= nrows || cols[i] >= npol) return KW_E_ARG;
   std::vector<uint64_t> table;

@@ -30,6 +30,12 @@ Status format_response(const Env& env, const Batch& b, uint64_t row, int32_t pid
 // the policy's missing required drops and default adds to every container, as compact JSON.
 Status capabilities_patch(const PolicyRec& P, const char* doc, size_t len, int doc_kind, std::string* ops);
 
+// The same patch from the batch's columns and its patch-shape columns (patches.cpp), without the
+// document: the ops (form KW_PATCH_OPS) or the whole response (KW_PATCH_RESPONSE) of (row, policy,
+// verdict). KW_E_ARG with a message that names what is missing: no KW_F_PATCH, a policy of another
+// family, an unknown pointer or shape.
+Status format_patch(const Env& env, const Batch& b, uint64_t row, int32_t pidx, uint32_t v, int form, std::string* out);
+
 // Host restatement of the image split used only for message text (registry / tag names).
 void image_parts(std::string_view image, std::string* registry, std::string* tag, bool* has_tag);
 

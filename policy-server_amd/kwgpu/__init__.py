@@ -943,6 +943,77 @@ class Batch:
         raise_for(self._L.kw_debug_responses_stats(self._h, out), "the batch never rendered responses")
         return dict(zip(("rounds", "windows", "spanning", "host", "uploaded_side", "escaped"), (int(x) for x in out)))
 
+    def patches(self, env, policies, rows, cols, form=N.KW_PATCH_RESPONSE, words=False, cap=None, host_cap=None):
+        """The JSONPatch of the items (rows[i], cols[i]) of the last all-pairs device pass over
+        `policies` (kw_batch_patches), rendered on the device from the columns and the patch-shape
+        columns: Messages(off, text, words, host). form KW_PATCH_RESPONSE: the whole AdmissionResponse
+        with the base64 patch, byte for byte format_response(doc=...)'s; KW_PATCH_OPS: the RFC 6902
+        ops. The items in `host` (no KW_F_PATCH, no psp-capabilities column, an unknown shape) have
+        no text here. `cap` and `host_cap` as for messages()."""
+        arr = env._array(policies)
+        return self._messages_call(
+            lambda r, c, n, st: self._L.kw_batch_patches(self._h, env._h, arr, len(policies), r, c, n, int(form), st),
+            rows, cols, words, cap, host_cap)
+
+    def patches_from_words(self, env, policies, words, rows, cols, form=N.KW_PATCH_RESPONSE, how=0, with_words=False, cap=None,
+                           host_cap=None):
+        """Diagnostic (kw_debug_patches_words): the same output on the host from full words
+        [rows][npol] and this batch's host columns. how=0: one format_patch per item (the reference);
+        how=1: the renderer the device runs, in its rounds and windows."""
+        import numpy as np
+        arr = env._array(policies)
+        npol = len(policies)
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        nrows = words.size // npol
+        wp = words.ctypes.data_as(C.POINTER(C.c_uint32))
+        return self._messages_call(
+            lambda r, c, n, st: self._L.kw_debug_patches_words(env._h, self._h, arr, npol, wp, nrows, r, c, n, int(form), how, st),
+            rows, cols, with_words, cap, host_cap)
+
+    def format_patch(self, env, row, policy, verdict, form=N.KW_PATCH_RESPONSE):
+        """One pair's patch from the host columns, without the document (kw_format_patch): the bytes
+        of the response (KW_PATCH_RESPONSE) or of the ops (KW_PATCH_OPS). Raises (KW_E_ARG) with a
+        message that names what is missing where patches() lists the item for the host."""
+        need = C.c_size_t()
+        buf = C.create_string_buffer(1 << 15)
+        for _ in (0, 1):
+            rc = self._L.kw_format_patch(env._h, self._h, int(row), env._idx(policy), int(verdict), int(form), buf, len(buf),
+                                         C.byref(need))
+            if rc != N.KW_E_NOSPACE:
+                break
+            buf = C.create_string_buffer(need.value + 1)
+        raise_for(rc, buf.value.decode(errors="replace"))
+        return buf.value
+
+    def set_patch_shape(self, ctr_place, req_place):
+        """Sets the patch-shape columns (kw_batch_set_patch_shape): per container
+        KW_PS_* << KW_PS_SHIFT | the item's index in its JSON array, per request KW_PP_*. A batch made
+        from columns holds "unknown" until this call; wrong sizes or codes raise."""
+        import numpy as np
+        cp = np.ascontiguousarray(ctr_place, dtype=np.uint32).reshape(-1)
+        rp = np.ascontiguousarray(req_place, dtype=np.uint8).reshape(-1)
+        raise_for(self._L.kw_batch_set_patch_shape(self._h, cp.ctypes.data_as(C.POINTER(C.c_uint32)), cp.size,
+                                                   rp.ctypes.data_as(C.POINTER(C.c_uint8)), rp.size),
+                  "the patch shape does not fit the batch")
+
+    def patch_shape(self):
+        """The patch-shape columns (kw_batch_patch_shape): (ctr_place u32 [containers], req_place u8 [rows])."""
+        import numpy as np
+        v = self.view()
+        cp = np.zeros(int(v.ctr_off[v.n_requests]) if v.n_requests else 0, dtype=np.uint32)
+        rp = np.zeros(int(v.n_requests), dtype=np.uint8)
+        raise_for(self._L.kw_batch_patch_shape(self._h, cp.ctypes.data_as(C.POINTER(C.c_uint32)), cp.size,
+                                               rp.ctypes.data_as(C.POINTER(C.c_uint8)), rp.size), "kw_batch_patch_shape failed")
+        return cp, rp
+
+    def debug_patches_stats(self):
+        """Diagnostic (kw_debug_patches_stats): what the last patches() did, as a dict: the rounds, the
+        staging windows written, the items that spanned a window, the items left to the host, whether
+        the call uploaded a side column."""
+        out = (C.c_uint64 * 5)()
+        raise_for(self._L.kw_debug_patches_stats(self._h, out), "the batch never rendered patches")
+        return dict(zip(("rounds", "windows", "spanning", "host", "uploaded_side"), (int(x) for x in out)))
+
     def finding_key(self, row, word):
         """The key bytes of the finding `word` at batch row `row` (kw_batch_finding_key), host only:
         (key, value) for KW_R_LABEL_CONSTRAINT, else (key, None); a numeric or empty key is b""."""

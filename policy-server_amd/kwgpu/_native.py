@@ -44,6 +44,13 @@ KW_F_PATCH = 0x40
 KW_FST_NONE, KW_FST_VANILLA, KW_FST_MUTATION_REFUSED, KW_FST_INIT_ERROR = 0, 1, 2, 3
 KW_ARG_WIDE = 0xFFFF
 
+# the patch-shape columns and the forms of kw_batch_patches (kwgpu.h)
+KW_PS_UNKNOWN, KW_PS_NO_SC, KW_PS_NO_CAPS, KW_PS_CAPS, KW_PS_MAX = 0, 1, 2, 3, 6
+KW_PS_ADD_ARRAY, KW_PS_DROP_ARRAY = 1, 2
+KW_PS_SHIFT, KW_PS_INDEX_MASK = 28, 0x0FFFFFFF
+KW_PP_UNKNOWN, KW_PP_NONE, KW_PP_POD, KW_PP_TEMPLATE, KW_PP_CRONJOB = 0, 1, 2, 3, 4
+KW_PATCH_OPS, KW_PATCH_RESPONSE = 0, 1
+
 # kw_summary counter indices (kwgpu.h)
 KW_SUM_F_ALLOWED, KW_SUM_V_ALLOWED, KW_SUM_V_MUTATED, KW_SUM_F_PATCH, KW_SUM_BYPASS = 0, 1, 2, 3, 4
 KW_SUM_FST_VANILLA, KW_SUM_FST_MUTATION_REFUSED, KW_SUM_FST_INIT_ERROR = 5, 6, 7
@@ -155,6 +162,8 @@ EXPORTS = [
     "kw_batch_digest_members", "kw_debug_digest_members_words",
     "kw_batch_messages", "kw_debug_messages_words", "kw_debug_messages_stats",
     "kw_batch_responses", "kw_debug_responses_words", "kw_debug_responses_stats",
+    "kw_batch_set_patch_shape", "kw_batch_patch_shape", "kw_format_patch", "kw_batch_patches", "kw_debug_patches_words",
+    "kw_debug_patches_stats",
     "kw_metrics_add_outcomes", "kw_metrics_record_pass", "kw_batch_pin_host", "kw_host_alloc", "kw_host_free",
     "kw_batch_destroy", "kw_debug_host_walk", "kw_validate_batch", "kw_validate_rows", "kw_batch_verdicts",
     "kw_validate_timed", "kw_format_response", "kw_format_response_doc", "kw_env_group_members", "kw_evaluate",
@@ -260,6 +269,13 @@ def lib():
         "kw_debug_responses_words": (ip, [vp, vp, C.POINTER(i32), u32, C.POINTER(u32), u64, C.POINTER(u64), C.POINTER(u32), sz, ip,
                                           C.POINTER(KwResponses)]),
         "kw_debug_responses_stats": (ip, [vp, C.POINTER(u64)]),
+        "kw_batch_set_patch_shape": (ip, [vp, C.POINTER(u32), u64, C.POINTER(C.c_uint8), u64]),
+        "kw_batch_patch_shape": (ip, [vp, C.POINTER(u32), u64, C.POINTER(C.c_uint8), u64]),
+        "kw_format_patch": (ip, [vp, vp, u64, i32, u32, ip, cp, sz, C.POINTER(sz)]),
+        "kw_batch_patches": (ip, [vp, vp, C.POINTER(i32), u32, C.POINTER(u64), C.POINTER(u32), sz, ip, C.POINTER(KwResponses)]),
+        "kw_debug_patches_words": (ip, [vp, vp, C.POINTER(i32), u32, C.POINTER(u32), u64, C.POINTER(u64), C.POINTER(u32), sz, ip, ip,
+                                        C.POINTER(KwResponses)]),
+        "kw_debug_patches_stats": (ip, [vp, C.POINTER(u64)]),
         "kw_metrics_add_outcomes": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64, C.POINTER(u64), u32, C.POINTER(u64)]),
         "kw_metrics_record_pass": (ip, [vp, vp, vp, C.POINTER(i32), u32, ip, u64]),
         "kw_batch_pin_host": (ip, [vp, ip]),
